@@ -2,8 +2,8 @@
 """Benchmark of the `autocycler compress` hot path on MI355X.
 
 Metric (BASELINE.json): Mbp/s through compress -> unitig graph (k=51), workload config C = 96 x ~5 Mbp synthetic
-assemblies on one GPU.  A "step" is one full pass of the replaced region (compress.rs:42-44).  Three brackets are timed in
-the same run and printed in the same JSON line; at N = 1:
+assemblies on one GPU.  A "step" is one full pass of the replaced region (compress.rs:42-44).  With --full, three brackets
+are timed in the same run and printed in the same JSON line; at N = 1:
 
   value / ms_per_step   T_hot of SURVEY.md 8(d), the bracket the metric and the >= 50x target are defined on: the padded,
                         end-repaired sequences in (pageable) HOST RAM -> final unitig graph (segments, links in L-line order,
@@ -19,7 +19,13 @@ the same run and printed in the same JSON line; at N = 1:
 plus cold_first_build_ms, the first build of this process (arena, pinned pools, code objects).  Input generation happens
 before all of them.
 
-    python bench.py [--gpus N --steps K --warmup W] [--assemblies 96 --genome 5000000 --kmer 51]
+A plain run times only the headline bracket (`value` / `ms_per_step`: T_hot at N = 1, the device-resident steps at N > 1 or with
+--no-host-bracket): inputs, untimed warm-up builds, K timed steps, the JSON line.  `--full` adds everything else: the other brackets,
+the per-stage breakdown, the host-entry == device-entry graph check, the roofline (PMC traffic, random-access ceilings), the CPU
+baseline and the golden md5 check, and at N > 1 the independent-jobs and in-library multi-device figures.
+`--dump-outputs DIR` writes what the last timed step built as DIR/<name>.npy (see dump_outputs).
+
+    python bench.py [--gpus N --steps K --warmup W] [--assemblies 96 --genome 5000000 --kmer 51] [--full] [--dump-outputs DIR]
 
 N > 1: launched by torch.distributed.run, one rank per GPU.  Default `--mode sharded`: ONE compress job of
 N x 96 assemblies, sequences sharded by rank (rank r holds assemblies 96r .. 96r+95), the job's k-mer table partitioned over the
@@ -142,6 +148,56 @@ def collect_pmc_live(n_text, tag="bench_live", timeout=420, workload=None):
         return {"error": repr(e)[:300]}
 
 
+DUMP_SAMPLE = 1 << 19      # elements kept of a larger array: 7 arrays + their indices stay under 64 MB
+DUMP_SEED = 51_000
+
+
+def dump_outputs(g, out_dir):
+    """--dump-outputs: the graph a caller of the timed build receives (Graph.bulk(): unitig sequences and depths, links, paths — what the
+    GFA holds) as out_dir/<name>.npy.  unitig_sequence (the unitigs' bases, ASCII codes, concatenated in unitig order) is float32, the
+    rest float64 (integers below 2^53 are exact).  An array of more than DUMP_SAMPLE elements is replaced by a fixed, seeded sample of
+    its elements, sorted by position, and <name>_index.npy holds their indices; summary.npy holds the whole arrays' sizes and sums."""
+    import zlib
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    b = g.bulk()
+    seq_len = b["seq_len"].astype(np.int64)
+    seq_end = np.cumsum(seq_len)
+    seq_start = seq_end - seq_len
+    n_bases = int(seq_end[-1]) if len(seq_end) else 0
+
+    def bases(idx):      # position in the concatenated unitig sequences -> base, whatever the library's own layout
+        u = np.searchsorted(seq_end, idx, side="right")
+        return b["seq_bytes"][b["seq_begin"][u].astype(np.int64) + (idx - seq_start[u])]
+
+    arrays = [("unitig_length", len(seq_len), lambda i: seq_len[i], np.float64),
+              ("unitig_depth", len(seq_len), lambda i: b["depth"][i], np.float64),
+              ("unitig_sequence", n_bases, bases, np.float32),
+              ("link_from", len(b["links"]), lambda i: b["links"]["a"][i], np.float64),      # signed unitig numbers: negative = reverse strand
+              ("link_to", len(b["links"]), lambda i: b["links"]["b"][i], np.float64),
+              ("path_entries", len(b["path_entries"]), lambda i: b["path_entries"][i], np.float64),
+              ("path_offsets", len(b["path_off"]), lambda i: b["path_off"][i], np.float64)]
+    total = 0
+    for name, n, get, dt in arrays:
+        idx = np.arange(n, dtype=np.int64)
+        if n > DUMP_SAMPLE:
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+            idx = np.unique(rng.integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+            np.save(out_dir / f"{name}_index.npy", idx.astype(np.float64))
+            total += idx.size * 8
+        np.save(out_dir / f"{name}.npy", np.asarray(get(idx)).astype(dt))
+        total += idx.size * np.dtype(dt).itemsize
+    chunk = 1 << 24
+    base_sum = sum(int(bases(np.arange(s, min(s + chunk, n_bases), dtype=np.int64)).sum(dtype=np.int64)) for s in range(0, n_bases, chunk))
+    link_sum = int(np.abs(b["links"]["a"]).sum(dtype=np.int64) + np.abs(b["links"]["b"]).sum(dtype=np.int64))
+    # unitigs, links, bases, k-mers, path entries, sequences; sums of the depths, the bases, the path entries and the |link ends|
+    summary = np.array([len(seq_len), len(b["links"]), n_bases, g.kmer_count, len(b["path_entries"]), len(b["path_off"]) - 1,
+                        b["depth"].sum(), base_sum, b["path_entries"].sum(dtype=np.int64), link_sum], dtype=np.float64)
+    np.save(out_dir / "summary.npy", summary)
+    assert total + summary.nbytes <= 64_000_000, total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -184,6 +240,11 @@ def main():
                          "the job to the single-device build — what the protocol itself costs before a byte moves")
     ap.add_argument("--gather-paths", action="store_true",
                     help="sharded mode: gather the paths of all sequences to rank 0 (default: every rank keeps its own P lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline bracket: the other brackets, stage breakdown, graph checks, roofline, CPU baseline and (N > 1) "
+                         "the independent-jobs and in-library figures; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step built (unitigs, links, paths) as DIR/<name>.npy, float32 / float64, under 64 MB")
     args = ap.parse_args()
 
     import torch
@@ -240,6 +301,9 @@ def main():
         mode = "single" if world == 1 else "sharded"
     if mode == "single" and world > 1:
         mode = "independent"
+    # the headline bracket: T_hot (host RAM -> host RAM) at N = 1, else the device-resident steps; a plain run times only that one
+    hot_headline = world == 1 and mode == "single" and not args.no_host_bracket
+    time_device_entry = args.full or not hot_headline
     t0 = time.time()
     if named:
         from autocycler_amd import synth as _synth
@@ -327,38 +391,44 @@ def main():
             cold_first_build_ms = (time.perf_counter() - tc) * 1e3
         i += 1
     init_builds_run = i
-    if os.environ.get("BENCH_STAGE_TIMING"):      # experiment: keep the per-stage syncs inside the timed loop
-        lib.ac_set_stage_timing(C.c_int(1))
-    for _ in range(args.warmup):
-        step().close()
-    barrier()
-    t_start = time.perf_counter()
-    tms = []
+    tms, step_s, stage_tms = [], [], []
     g = None
-    step_s = []
-    for _ in range(args.steps):
-        ts = time.perf_counter()
-        if g is not None:
+    elapsed = None
+    graph_info = None
+    if time_device_entry:      # the device-resident bracket: the headline at N > 1 / --no-host-bracket, `hbm_resident` under --full
+        if os.environ.get("BENCH_STAGE_TIMING"):      # experiment: keep the per-stage syncs inside the timed loop
+            lib.ac_set_stage_timing(C.c_int(1))
+        for _ in range(args.warmup):
+            step().close()
+        barrier()
+        t_start = time.perf_counter()
+        for _ in range(args.steps):
+            ts = time.perf_counter()
+            if g is not None:
+                g.close()
+            g = step()
+            step_s.append(time.perf_counter() - ts)      # the build call returns with the graph in host RAM
+            tms.append(g.timings())
+        barrier()
+        elapsed = time.perf_counter() - t_start
+        if not hot_headline:
+            graph_info = {**g.stats_post, "kmers": g.kmer_count}
+            if args.dump_outputs and rank == 0:
+                dump_outputs(g, args.dump_outputs)
+    if args.full:
+        # stage breakdown from two extra, untimed, instrumented builds (a stream sync per stage costs ~0.3 ms per build)
+        lib.ac_set_stage_timing(C.c_int(1))
+        for _ in range(2):
             g.close()
-        g = step()
-        step_s.append(time.perf_counter() - ts)      # the build call returns with the graph in host RAM
-        tms.append(g.timings())
-    barrier()
-    elapsed = time.perf_counter() - t_start
-    # stage breakdown from two extra, untimed, instrumented builds (a stream sync per stage costs ~0.3 ms per build)
-    lib.ac_set_stage_timing(C.c_int(1))
-    stage_tms = []
-    for _ in range(2):
-        g.close()
-        g = step()
-        stage_tms.append(g.timings())
-    lib.ac_set_stage_timing(C.c_int(0))
-    barrier()
+            g = step()
+            stage_tms.append(g.timings())
+        lib.ac_set_stage_timing(C.c_int(0))
+        barrier()
 
     # ---- T_hot: the same sequences in host RAM -> final graph in host RAM through ac_compress_build ------------
     t_hot = None
     tms_hot = []
-    if world == 1 and mode == "single" and not args.no_host_bracket:
+    if hot_headline:
         import hashlib
         # what the Rust caller holds at compress.rs:41: the padded, end-repaired forward sequences in ordinary (pageable) host
         # memory — here the repaired device text read back, one view per sequence
@@ -376,13 +446,14 @@ def main():
                 raise RuntimeError(lib.ac_last_error().decode())
             return _capi.Graph(lib, h, n)
 
-        md5_dev = hashlib.md5(g.gfa(fn, hd).encode()).hexdigest()
         tc = time.perf_counter()
         gh = step_host()
         first_host_ms = (time.perf_counter() - tc) * 1e3      # allocates the pinned staging ring
-        md5_host = hashlib.md5(gh.gfa(fn, hd).encode()).hexdigest()
-        if md5_host != md5_dev:
-            raise SystemExit(f"host entry and device entry built different graphs: {md5_host} != {md5_dev}")
+        if args.full:
+            md5_dev = hashlib.md5(g.gfa(fn, hd).encode()).hexdigest()
+            md5_host = hashlib.md5(gh.gfa(fn, hd).encode()).hexdigest()
+            if md5_host != md5_dev:
+                raise SystemExit(f"host entry and device entry built different graphs: {md5_host} != {md5_dev}")
         gh.close()
         for _ in range(max(args.warmup, 1)):
             step_host().close()
@@ -400,6 +471,9 @@ def main():
             hup.append(tms_hot[-1]["h2d"]); hupd.append(tms_hot[-1]["upload_device_ms"])
         barrier()
         e_hot = time.perf_counter() - th0
+        graph_info = {**gh.stats_post, "kmers": gh.kmer_count}
+        if args.dump_outputs:
+            dump_outputs(gh, args.dump_outputs)
         gh.close()
         t_hot = {"value": bases / 1e6 / (e_hot / args.steps), "unit": "Mbp/s", "ms_per_step": e_hot / args.steps * 1e3, "steps": args.steps,
                  "elapsed_s": e_hot, "step_ms_list": [round(x * 1e3, 2) for x in hs],
@@ -412,12 +486,14 @@ def main():
                  "upload_ms": sum(hupd) / len(hupd), "upload_GBps": (n_text / (sum(hupd) / len(hupd) * 1e-3) / 1e9) if sum(hupd) else None,      # text bytes per second
                  "upload_pcie_GBps": (0.25 * n_text / (sum(hupd) / len(hupd) * 1e-3) / 1e9) if sum(hupd) else None,      # what crosses the link: 2 bits per base
                  "upload_host_side_ms": sum(hup) / len(hup) * 1e3,      # (until the build thread has the first chunk: the rest is sent in the background)
-                 "first_call_ms": first_host_ms, "gfa_md5": md5_host, "same_graph_as_device_entry": True}
+                 "first_call_ms": first_host_ms}
+        if args.full:
+            t_hot.update({"gfa_md5": md5_host, "same_graph_as_device_entry": True})
         del text_host
 
     # ---- T_e2e: the whole command on a FASTA directory (compress.rs:34 -> :49) -----------------------------------------------------
     t_e2e = None
-    if world == 1 and mode == "single" and not args.no_e2e and not emu_lib:
+    if args.full and world == 1 and mode == "single" and not args.no_e2e and not emu_lib:
         import hashlib
         import shutil
         import subprocess
@@ -469,11 +545,10 @@ def main():
     else:
         total_bases = float(bases)
 
-    graph_info = {**g.stats_post, "kmers": g.kmer_count}
     # Secondary figure at N > 1 (not `value`): the same ranks running their slices as N independent compress jobs — no
     # data-path collective — timed the same way, so that the cost of making it ONE job is visible in the same line.
     independent = None
-    if world > 1 and mode == "sharded" and not args.no_independent:
+    if args.full and world > 1 and mode == "sharded" and not args.no_independent:
         def step_ind():
             h = C.c_void_p()
             rc = lib.ac_compress_build_device(C.c_uint32(k), C.c_uint32(args.assemblies), C.c_void_p(d_text.data_ptr()),
@@ -499,7 +574,7 @@ def main():
     # devices through ac_compress_build_multi (in-library RCCL).  It runs in a subprocess of rank 0 while the other ranks wait (they give their
     # device memory back first), so whatever happens to it cannot take the benchmark line with it.
     in_library = None
-    if world > 1 and mode == "sharded" and not args.no_multi_entry and not emu_lib:
+    if args.full and world > 1 and mode == "sharded" and not args.no_multi_entry and not emu_lib:
         if g is not None:
             g.close(); g = None
         del d_text
@@ -521,12 +596,14 @@ def main():
 
     if rank == 0:
         # The headline: SURVEY.md 8(d)'s T_hot bracket (host RAM -> host RAM through ac_compress_build) wherever it was timed (N = 1);
-        # the device-resident bracket is the extra key `hbm_resident`.  N > 1 (and --no-host-bracket): the device-resident steps.
-        hbm_resident = {"value": total_bases / 1e6 / (elapsed / args.steps), "unit": "Mbp/s", "ms_per_step": elapsed / args.steps * 1e3, "steps": args.steps,
-                        "timed_region": "padded+repaired text RESIDENT IN HBM -> final unitig graph in host RAM (ac_compress_build_device: device build + D2H)",
-                        "step_ms_list": [round(x * 1e3, 2) for x in step_s],
-                        "step_ms": {"min": min(step_s) * 1e3, "median": sorted(step_s)[len(step_s) // 2] * 1e3, "max": max(step_s) * 1e3},
-                        "total_device_timed_ms": sum(t["total_device"] for t in tms) / len(tms) * 1e3}
+        # the device-resident bracket is the extra key `hbm_resident` (--full).  N > 1 (and --no-host-bracket): the device-resident steps.
+        hbm_resident = None
+        if time_device_entry:
+            hbm_resident = {"value": total_bases / 1e6 / (elapsed / args.steps), "unit": "Mbp/s", "ms_per_step": elapsed / args.steps * 1e3, "steps": args.steps,
+                            "timed_region": "padded+repaired text RESIDENT IN HBM -> final unitig graph in host RAM (ac_compress_build_device: device build + D2H)",
+                            "step_ms_list": [round(x * 1e3, 2) for x in step_s],
+                            "step_ms": {"min": min(step_s) * 1e3, "median": sorted(step_s)[len(step_s) // 2] * 1e3, "max": max(step_s) * 1e3},
+                            "total_device_timed_ms": sum(t["total_device"] for t in tms) / len(tms) * 1e3}
         headline_is_hot = t_hot is not None
         if headline_is_hot:
             elapsed_head, tms_head, step_head = t_hot["elapsed_s"], tms_hot, t_hot["step_ms_list"]
@@ -534,41 +611,7 @@ def main():
             elapsed_head, tms_head, step_head = elapsed, tms, hbm_resident["step_ms_list"]
         ms_per_step = elapsed_head / args.steps * 1e3
         value = total_bases / 1e6 / (elapsed_head / args.steps)
-        ins_ms = sum(t["insert_kernel_ms"] for t in tms_head) / len(tms_head)
-        if emu_lib and ins_ms <= 0:
-            ins_ms = 1e-3      # the emulation has no HIP events
-        alg_bytes = A_K(k) * bases      # one (key, tag) record written and read per input base — kept as `whole_path_equiv` only
-        # HBM bytes per build of the big kernels from the PMC passes (collected separately with tools/pmc_lean.sh and committed under
-        # profiles/; rocprofv3 counters cannot be read from inside this process).  Only quoted when this run is the workload the
-        # counters were collected on.
-        pj, traffic_src, pmc_note = None, None, None
-        pmc = ROOT / "profiles" / (f"pmc_traffic_{args.workload}.json" if named else "pmc_traffic.json")
-        default_workload = (args.assemblies, args.genome, args.plasmid, args.sub, args.indel, k) == (96, 5_000_000, 100_000, 1e-4, 1e-5, 51) and not named
-        if emu_lib and os.environ.get("BENCH_EMU_ASSUME_DEFAULT"):
-            default_workload = True      # dry run only: exercise the fields that are quoted for the default workload
-        counted_workload = default_workload or bool(named)      # the workloads tools/pmc_lean.sh can rebuild: config C and the named ones
-        lib.ac_source_hash.restype = C.c_char_p
-        lib_hash = lib.ac_source_hash().decode()
-        if counted_workload and args.pmc != "off":
-            if pmc.exists() and args.pmc != "live":
-                cand = json.loads(pmc.read_text())
-                if cand.get("source_hash") == lib_hash or (emu_lib and os.environ.get("BENCH_EMU_ASSUME_DEFAULT")):
-                    pj = cand
-                    traffic_src = (f"profiles/{pmc.name}: rocprofv3 PMC passes (tools/pmc_lean.sh) on a library built from exactly these sources "
-                                   f"(source hash {lib_hash}); FETCH_SIZE x2 per the gfx950 calibration, + WRITE_SIZE")
-                else:
-                    pmc_note = (f"profiles/{pmc.name} is stale: collected on sources {cand.get('source_hash')}, this library is {lib_hash}")
-            if pj is None and args.pmc in ("auto", "live") and not emu_lib and world == 1:
-                live = collect_pmc_live(n_text, workload=args.workload)
-                if "error" in live:
-                    pmc_note = ((pmc_note + "; ") if pmc_note else "") + "live collection failed: " + live["error"]
-                else:
-                    pj = live
-                    traffic_src = ("counted in this run: two rocprofv3 PMC passes (tools/pmc_lean.sh: FETCH_SIZE, WRITE_SIZE, --kernel-trace only) of the torch-free "
-                                   "driver building this workload with this library; FETCH_SIZE x2 per the gfx950 calibration, + WRITE_SIZE")
-        stage = {key: sum(t[key] for t in stage_tms) / len(stage_tms) for key in
-                 ("pack", "insert", "collect_sort", "degree", "segment", "minkey", "rank", "links", "paths", "seqs", "analysis", "expand", "finalize", "d2h",
-                  "total_device") + (("fragments", "union_pack", "union_insert") if mode == "sharded" else ())}
+        tm_last = (tms or tms_head)[-1]      # the last timed step's counters (the device-entry bracket's whenever it was timed)
         sharding = {"single": "one device", "independent": "by assembly set, one unrelated compress job per GPU",
                     "sharded": "ONE job: sequences sharded by rank, the k-mer table partitioned over the ranks by key hash (owner = hash of the "
                                "canonical middle): all-gather of novel-run fragments, SUM all-reduces of the owners' bitmap / degree / link "
@@ -600,137 +643,175 @@ def main():
                                         "ac_compress_build (host-side 2-bit pack, H2D, device build, D2H); the same region with the text already resident "
                                         "in HBM is `hbm_resident`, the whole command `t_e2e`") if headline_is_hot else
                                        ("padded+repaired sequences in HBM -> final unitig graph in host RAM (device build + D2H)")},
-            "roofline": None,      # (filled in below)
+            "roofline": None,      # (--full: filled in below)
             "hbm_resident": hbm_resident,
             "t_hot": t_hot, "t_e2e": t_e2e, "cold_first_build_ms": cold_first_build_ms, "init_builds_run": init_builds_run,
-            "untimed_builds_before_the_timed_steps": {"init": init_builds_run, "warmup_device_entry": args.warmup, "device_entry_steps": args.steps + 2,
+            "untimed_builds_before_the_timed_steps": {"init": init_builds_run, "warmup_device_entry": args.warmup if time_device_entry else 0,
+                                                      "device_entry_steps": (args.steps + 2 if args.full else args.steps) if time_device_entry else 0,
                                                       "first_host_entry_call": 1 if headline_is_hot else 0, "warmup_host_entry": max(args.warmup, 1) if headline_is_hot else 0},
             "total_device_timed_ms": sum(t["total_device"] for t in tms_head) / len(tms_head) * 1e3,
             "step_ms_list": step_head,
             "step_ms": {"min": min(step_head), "median": sorted(step_head)[len(step_head) // 2], "max": max(step_head)},
-            "launches_per_build": tms[-1].get("launches"), "host_round_trips_per_build": tms[-1].get("readbacks"),
-            "stages_s": stage, "stages_note": "from 2 extra untimed builds with per-stage stream syncs (total_device there includes them)",
-            "graph": {**graph_info, "distinct_canonical": tms[-1]["n_distinct"],
-                      "path_entries": tms[-1]["n_path_entries"], "table_capacity": tms[-1]["table_capacity"],
-                      "simplify_passes": tms[-1]["simplify_passes"]},
+            "launches_per_build": tm_last.get("launches"), "host_round_trips_per_build": tm_last.get("readbacks"),
+            "graph": {**graph_info, "distinct_canonical": tm_last["n_distinct"],
+                      "path_entries": tm_last["n_path_entries"], "table_capacity": tm_last["table_capacity"],
+                      "simplify_passes": tm_last["simplify_passes"]},
             "prep_s": {"generate": t_gen, "end_repair": t_repair, "end_repair_info": repair_info, "h2d": t_h2d, "h2d_GBps": n_text / t_h2d / 1e9},
         }
-        # ---- roofline ---------------------------------------------------------------------------------------------------------------------
-        # Per kernel: `traffic` = HBM-side bytes per build from the PMC passes, `frac` = traffic / time / 8 TB/s (a measured fraction, <= 1);
-        # `needed_bytes` = a LOWER bound on the bytes this algorithm has to move (model stated in `needed_model`), `achieved` = needed_bytes /
-        # time, `waste` = traffic / needed_bytes (re-reads and partial lines); `ceiling` = what actually binds the kernel, by name, with the
-        # share of the kernel's time the unavoidable operations of that kind take at the device's measured rate.  The SURVEY.md 8(d) figure
-        # (49 B/bp at k = 51: a (key, tag) record written and read per input base) is only kept as `whole_path_equiv`: the run-following
-        # insert never materialises those records, so dividing them by the insert's time gives a "fraction" above 1 (round 2: 3.13).
-        cas, rd = C.c_double(), C.c_double()
-        st = tms_head[-1]
-        # (measured on a table of the size this workload's k-mer table has: beyond the 256 MB Infinity Cache the claim rate drops)
-        ceil_slots = int(st.get("table_capacity") or (1 << 24))
-        have_ceil = lib.ac_random_access_ceilings_at(C.c_int(local_rank), C.c_uint64(ceil_slots), C.byref(cas), C.byref(rd)) == 0 and cas.value > 0
-        claims = st["n_local_distinct"] or st["n_distinct"]
-        U_now = graph_info["unitigs"]
-        per_kernel = (pj or {}).get("per_kernel_per_build", {})
-        pmc_of = lambda pat: sum(v["hbm_side_bytes"] for kk, v in per_kernel.items() if pat in kk) or None
+        if args.full:
+            ins_ms = sum(t["insert_kernel_ms"] for t in tms_head) / len(tms_head)
+            if emu_lib and ins_ms <= 0:
+                ins_ms = 1e-3      # the emulation has no HIP events
+            alg_bytes = A_K(k) * bases      # one (key, tag) record written and read per input base — kept as `whole_path_equiv` only
+            # HBM bytes per build of the big kernels from the PMC passes (collected separately with tools/pmc_lean.sh and committed under
+            # profiles/; rocprofv3 counters cannot be read from inside this process).  Only quoted when this run is the workload the
+            # counters were collected on.
+            pj, traffic_src, pmc_note = None, None, None
+            pmc = ROOT / "profiles" / (f"pmc_traffic_{args.workload}.json" if named else "pmc_traffic.json")
+            default_workload = (args.assemblies, args.genome, args.plasmid, args.sub, args.indel, k) == (96, 5_000_000, 100_000, 1e-4, 1e-5, 51) and not named
+            if emu_lib and os.environ.get("BENCH_EMU_ASSUME_DEFAULT"):
+                default_workload = True      # dry run only: exercise the fields that are quoted for the default workload
+            counted_workload = default_workload or bool(named)      # the workloads tools/pmc_lean.sh can rebuild: config C and the named ones
+            lib.ac_source_hash.restype = C.c_char_p
+            lib_hash = lib.ac_source_hash().decode()
+            if counted_workload and args.pmc != "off":
+                if pmc.exists() and args.pmc != "live":
+                    cand = json.loads(pmc.read_text())
+                    if cand.get("source_hash") == lib_hash or (emu_lib and os.environ.get("BENCH_EMU_ASSUME_DEFAULT")):
+                        pj = cand
+                        traffic_src = (f"profiles/{pmc.name}: rocprofv3 PMC passes (tools/pmc_lean.sh) on a library built from exactly these sources "
+                                       f"(source hash {lib_hash}); FETCH_SIZE x2 per the gfx950 calibration, + WRITE_SIZE")
+                    else:
+                        pmc_note = (f"profiles/{pmc.name} is stale: collected on sources {cand.get('source_hash')}, this library is {lib_hash}")
+                if pj is None and args.pmc in ("auto", "live") and not emu_lib and world == 1:
+                    live = collect_pmc_live(n_text, workload=args.workload)
+                    if "error" in live:
+                        pmc_note = ((pmc_note + "; ") if pmc_note else "") + "live collection failed: " + live["error"]
+                    else:
+                        pj = live
+                        traffic_src = ("counted in this run: two rocprofv3 PMC passes (tools/pmc_lean.sh: FETCH_SIZE, WRITE_SIZE, --kernel-trace only) of the torch-free "
+                                       "driver building this workload with this library; FETCH_SIZE x2 per the gfx950 calibration, + WRITE_SIZE")
+            stage = {key: sum(t[key] for t in stage_tms) / len(stage_tms) for key in
+                     ("pack", "insert", "collect_sort", "degree", "segment", "minkey", "rank", "links", "paths", "seqs", "analysis", "expand", "finalize", "d2h",
+                      "total_device") + (("fragments", "union_pack", "union_insert") if mode == "sharded" else ())}
+            line["stages_s"] = stage
+            line["stages_note"] = "from 2 extra untimed builds with per-stage stream syncs (total_device there includes them)"
+            # ---- roofline ---------------------------------------------------------------------------------------------------------------------
+            # Per kernel: `traffic` = HBM-side bytes per build from the PMC passes, `frac` = traffic / time / 8 TB/s (a measured fraction, <= 1);
+            # `needed_bytes` = a LOWER bound on the bytes this algorithm has to move (model stated in `needed_model`), `achieved` = needed_bytes /
+            # time, `waste` = traffic / needed_bytes (re-reads and partial lines); `ceiling` = what actually binds the kernel, by name, with the
+            # share of the kernel's time the unavoidable operations of that kind take at the device's measured rate.  The SURVEY.md 8(d) figure
+            # (49 B/bp at k = 51: a (key, tag) record written and read per input base) is only kept as `whole_path_equiv`: the run-following
+            # insert never materialises those records, so dividing them by the insert's time gives a "fraction" above 1 (round 2: 3.13).
+            cas, rd = C.c_double(), C.c_double()
+            st = tms_head[-1]
+            # (measured on a table of the size this workload's k-mer table has: beyond the 256 MB Infinity Cache the claim rate drops)
+            ceil_slots = int(st.get("table_capacity") or (1 << 24))
+            have_ceil = lib.ac_random_access_ceilings_at(C.c_int(local_rank), C.c_uint64(ceil_slots), C.byref(cas), C.byref(rd)) == 0 and cas.value > 0
+            claims = st["n_local_distinct"] or st["n_distinct"]
+            U_now = graph_info["unitigs"]
+            per_kernel = (pj or {}).get("per_kernel_per_build", {})
+            pmc_of = lambda pat: sum(v["hbm_side_bytes"] for kk, v in per_kernel.items() if pat in kk) or None
 
-        def roof(kernel, what, ms, needed, model, traffic, ceiling):
-            r = {"bound": "hbm", "kernel": kernel, "what": what, "kernel_ms": ms, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                 "needed_bytes": needed, "needed_model": model, "achieved": needed / (ms * 1e-3) / 1e9 if ms else None,
-                 "frac_needed": needed / (ms * 1e-3) / HBM_PEAK if ms else None,
-                 "traffic": traffic, "traffic_source": traffic_src if traffic else None,
-                 "traffic_GBps": traffic / (ms * 1e-3) / 1e9 if (traffic and ms) else None,
-                 "waste": traffic / needed if traffic else None, "ceiling": ceiling}
-            # the fraction of the HBM peak: measured bytes where the counters exist for this workload, else the model's lower bound
-            r["frac"] = (traffic / (ms * 1e-3) / HBM_PEAK) if (traffic and ms) else r["frac_needed"]
-            r["frac_source"] = "traffic (PMC) / kernel time / peak" if traffic else "needed_bytes (model, a lower bound) / kernel time / peak"
-            return r
+            def roof(kernel, what, ms, needed, model, traffic, ceiling):
+                r = {"bound": "hbm", "kernel": kernel, "what": what, "kernel_ms": ms, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                     "needed_bytes": needed, "needed_model": model, "achieved": needed / (ms * 1e-3) / 1e9 if ms else None,
+                     "frac_needed": needed / (ms * 1e-3) / HBM_PEAK if ms else None,
+                     "traffic": traffic, "traffic_source": traffic_src if traffic else None,
+                     "traffic_GBps": traffic / (ms * 1e-3) / 1e9 if (traffic and ms) else None,
+                     "waste": traffic / needed if traffic else None, "ceiling": ceiling}
+                # the fraction of the HBM peak: measured bytes where the counters exist for this workload, else the model's lower bound
+                r["frac"] = (traffic / (ms * 1e-3) / HBM_PEAK) if (traffic and ms) else r["frac_needed"]
+                r["frac_source"] = "traffic (PMC) / kernel time / peak" if traffic else "needed_bytes (model, a lower bound) / kernel time / peak"
+                return r
 
-        packed_b = 0.375 * n_text      # 2 bits of code + 1 mask bit per text position
-        ins_needed = 2 * packed_b + 64.0 * claims + n_text / 8.0
-        ins_ceiling = None
-        if have_ceil:
-            ins_ceiling = {"name": "cas", "rate_Gops": cas.value, "operations": claims, "bound_ms": claims / cas.value / 1e6,
-                           "frac": claims / cas.value / 1e6 / ins_ms,
-                           "table_slots": ceil_slots,
-                           "note": "one atomicCAS per distinct k-mer at the device's measured random-CAS rate on a table of this workload's table size: "
-                                   "the share of the kernel's time that no insert into a hash table with random placement can avoid"}
-        line["roofline"] = roof(
-            "insert_wave_kernel<W> (wavefront-cooperative run-following k-mer insert; %d phase launches per build)" % st["insert_launches"],
-            "KmerGraph::add_sequences (kmer_graph.rs:86-134) + iterate_kmers' key set", ins_ms, ins_needed,
-            "packed text (0.375 B per position) read on both sides of a followed run + one 64-byte slot line per distinct k-mer + the novel bitmap "
-            "(1 bit per position)", pmc_of("insert_wave_kernel"), ins_ceiling)
-        line["roofline"]["library_source_hash"] = lib_hash
-        if pj and pj.get("traffic_raw"):      # the raw counter, the streaming-calibrated upper bound and the factor actually applied
-            raw, x2 = pj["traffic_raw"], pj.get("traffic_streaming_x2") or pj["traffic_raw"]
-            line["roofline"]["traffic_raw"] = raw
-            line["roofline"]["traffic_streaming_x2"] = x2
-            line["roofline"]["fetch_factor_applied"] = pj.get("fetch_correction")
-            line["roofline"]["fetch_factor_calibration"] = pj.get("calibration_random") or "streaming (PackFunctor) only: no random-access calibration file for these sources"
-            line["roofline"]["frac_range"] = [raw / (ins_ms * 1e-3) / HBM_PEAK, x2 / (ins_ms * 1e-3) / HBM_PEAK]
-        if pmc_note:
-            line["roofline"]["traffic_note"] = pmc_note
-        line["roofline"]["whole_path_equiv"] = {"bytes": alg_bytes, "B_per_bp": A_K(k), "frac_of_peak_over_the_whole_step": alg_bytes / (elapsed_head / args.steps) / HBM_PEAK,
-                                                "note": "SURVEY.md 8(d) accounting (a sort-based design's record traffic) over the WHOLE timed step, not over the insert kernel"}
-        others = []
-        n_ent = st["n_path_entries"]
-        walk_ms = stage["paths"] * 1e3
-        walk_ceiling = None
-        if have_ceil:
-            n_walkers = n_text / 256.0
-            ops = n_ent + 9.0 * n_walkers      # one successor-table gather per entry + the ~9 dependent lines of each walker's start-up lookup
-            walk_ceiling = {"name": "random_read", "rate_Gops": rd.value, "operations": ops, "bound_ms": ops / rd.value / 1e6,
-                            "frac": ops / rd.value / 1e6 / walk_ms if walk_ms else None,
-                            "note": "one dependent gather per path entry plus each walker's start-up lookup, at the device's measured random 8-byte read rate"}
-        if st.get("path_runs_copied", 0) > 0:
-            # the copying walk (chosen by the library's cost model on large redundant texts): the text between the insert's
-            # followed runs is walked, the runs' entries are copied from the walked entries of the stretch they repeat
-            copy_kernels = ("PathWalkFunctor", "RunOutFunctor", "GapOutFunctor", "WalkCompactFunctor", "RunRangeFunctor", "RunFilterFunctor",
-                            "RunGatherFunctor", "RunCompactFunctor", "GapWalkersFunctor", "WalkerRangeFunctor", "SegCountFunctor", "WlinkFlagFunctor",
-                            "WalkInfoFunctor", "MaybeDestFunctor", "PathOffCopyFunctor", "PathEndsFunctor")
-            walked = st["path_entries_walked"]
-            n_steps = 28      # ~24 dependent launches + 4 read-backs in the stage (profiles/r09e_timeline_path_copy_rows.txt)
-            others.append(roof("copying path walk: PathWalkFunctor<W> over the gaps + RunOutFunctor / GapOutFunctor + run bookkeeping (stage `paths`)",
-                               "get_unitig_path_for_sequence (unitig_graph.rs:407-465) for all sequences",
-                               walk_ms, 8.0 * n_ent + 24.0 * st["path_runs_copied"] + packed_b * (walked / max(n_ent, 1)) + 96.0 * U_now,
-                               "every path entry read once from the walked entries and written once (2 x 4 B) + 24 B per copied run + the walked share of "
-                               "the packed text read once + the unitig / successor records (96 B per unitig) read once",
-                               sum(pmc_of(nm) or 0 for nm in copy_kernels) or None,
-                               {"name": "dependent_launches", "operations": n_steps, "bound_ms": n_steps * 0.010, "frac": n_steps * 0.010 / walk_ms if walk_ms else None,
-                                "note": "kernels and host read-backs that must follow one another (scan -> size -> launch), ~10 us each: the stage's floor once "
-                                        "its per-entry work is streaming copies; %d of %d entries were walked, the rest copied" % (walked, n_ent)}))
-        else:
-            others.append(roof("PathWalkFunctor<W> + PathCompactFunctor (stage `paths`)", "get_unitig_path_for_sequence (unitig_graph.rs:407-465) for all sequences",
-                               walk_ms, 8.0 * n_ent + packed_b + 96.0 * U_now,
-                               "every path entry written to its staging slot and once more in text order (2 x 4 B) + the packed text read once + the unitig / "
-                               "successor records (96 B per unitig) read once",
-                               (pmc_of("PathWalkFunctor") or 0) + (pmc_of("PathCompactFunctor") or 0) or None, walk_ceiling))
-        exp_ms = stage["expand"] * 1e3
-        n_cand = st["n_candidates"]
-        n_launch = st["n_levels"] * st["simplify_passes"]
-        others.append(roof("expand_wave_kernel<W,16> + level scheduling + sequence rewrite (stage `expand`)",
-                           "expand_repeats (graph_simplification.rs:43-86)", exp_ms, n_cand * (120.0 + 5 * 64.0) + 2.0 * graph_info["total_length"],
-                           "per candidate junction once: its link row and five source records (120 B) + one 64-byte line of each source's sequence; the "
-                           "sequences rewritten once after the last pass (read + write)",
-                           pmc_of("expand_wave_kernel"),
-                           {"name": "dependent_launches", "operations": n_launch, "bound_ms": n_launch * 0.010, "frac": n_launch * 0.010 / exp_ms if exp_ms else None,
-                            "note": "levels x passes kernels that must run one after the other (the reference's visiting order), ~10 us each: junction chains, "
-                                    "not bytes, bind this stage"}))
-        line["roofline_other"] = others
-        # The kernels of this path are bound by random accesses into the k-mer table, not by streamed bytes: price them against
-        # the device's measured random-access ceilings as well (a ~20 ms microbenchmark inside the library).
-        if have_ceil:
-            deg_ms = stage["degree"] * 1e3
-            line["random_access"] = {
-                "cas_ceiling_Gops": cas.value, "read_ceiling_Gops": rd.value, "measured_on_table_slots": ceil_slots,
-                "insert": {"slot_claims": st["n_local_distinct"] or st["n_distinct"], "kernel_ms": ins_ms,
-                           "claims_only_bound_ms": (st["n_local_distinct"] or st["n_distinct"]) / cas.value / 1e6,
-                           "frac_of_cas_ceiling": (st["n_local_distinct"] or st["n_distinct"]) / cas.value / 1e6 / ins_ms},
-                "degree": {"stage_ms": deg_ms, "walks_if_every_degree_were_probed": 2 * st["n_distinct"],
-                           "walks_only_bound_ms": 2 * st["n_distinct"] / rd.value / 1e6,
-                           "stage_over_that_bound": deg_ms / (2 * st["n_distinct"] / rd.value / 1e6)},
-                "note": "bounds count only the unavoidable random accesses: one CAS per distinct k-mer for the insert; for the degree pass "
-                        "the two probe-cluster walks per distinct k-mer it WOULD need if every degree were probed (round 1-2 form) — the "
-                        "single-device pass settles nearly all of them from the sibling bits the insert collects (DESIGN.md section 4, K5) and only "
-                        "probes the rest, which is why the stage can be faster than that bound"}
+            packed_b = 0.375 * n_text      # 2 bits of code + 1 mask bit per text position
+            ins_needed = 2 * packed_b + 64.0 * claims + n_text / 8.0
+            ins_ceiling = None
+            if have_ceil:
+                ins_ceiling = {"name": "cas", "rate_Gops": cas.value, "operations": claims, "bound_ms": claims / cas.value / 1e6,
+                               "frac": claims / cas.value / 1e6 / ins_ms,
+                               "table_slots": ceil_slots,
+                               "note": "one atomicCAS per distinct k-mer at the device's measured random-CAS rate on a table of this workload's table size: "
+                                       "the share of the kernel's time that no insert into a hash table with random placement can avoid"}
+            line["roofline"] = roof(
+                "insert_wave_kernel<W> (wavefront-cooperative run-following k-mer insert; %d phase launches per build)" % st["insert_launches"],
+                "KmerGraph::add_sequences (kmer_graph.rs:86-134) + iterate_kmers' key set", ins_ms, ins_needed,
+                "packed text (0.375 B per position) read on both sides of a followed run + one 64-byte slot line per distinct k-mer + the novel bitmap "
+                "(1 bit per position)", pmc_of("insert_wave_kernel"), ins_ceiling)
+            line["roofline"]["library_source_hash"] = lib_hash
+            if pj and pj.get("traffic_raw"):      # the raw counter, the streaming-calibrated upper bound and the factor actually applied
+                raw, x2 = pj["traffic_raw"], pj.get("traffic_streaming_x2") or pj["traffic_raw"]
+                line["roofline"]["traffic_raw"] = raw
+                line["roofline"]["traffic_streaming_x2"] = x2
+                line["roofline"]["fetch_factor_applied"] = pj.get("fetch_correction")
+                line["roofline"]["fetch_factor_calibration"] = pj.get("calibration_random") or "streaming (PackFunctor) only: no random-access calibration file for these sources"
+                line["roofline"]["frac_range"] = [raw / (ins_ms * 1e-3) / HBM_PEAK, x2 / (ins_ms * 1e-3) / HBM_PEAK]
+            if pmc_note:
+                line["roofline"]["traffic_note"] = pmc_note
+            line["roofline"]["whole_path_equiv"] = {"bytes": alg_bytes, "B_per_bp": A_K(k), "frac_of_peak_over_the_whole_step": alg_bytes / (elapsed_head / args.steps) / HBM_PEAK,
+                                                    "note": "SURVEY.md 8(d) accounting (a sort-based design's record traffic) over the WHOLE timed step, not over the insert kernel"}
+            others = []
+            n_ent = st["n_path_entries"]
+            walk_ms = stage["paths"] * 1e3
+            walk_ceiling = None
+            if have_ceil:
+                n_walkers = n_text / 256.0
+                ops = n_ent + 9.0 * n_walkers      # one successor-table gather per entry + the ~9 dependent lines of each walker's start-up lookup
+                walk_ceiling = {"name": "random_read", "rate_Gops": rd.value, "operations": ops, "bound_ms": ops / rd.value / 1e6,
+                                "frac": ops / rd.value / 1e6 / walk_ms if walk_ms else None,
+                                "note": "one dependent gather per path entry plus each walker's start-up lookup, at the device's measured random 8-byte read rate"}
+            if st.get("path_runs_copied", 0) > 0:
+                # the copying walk (chosen by the library's cost model on large redundant texts): the text between the insert's
+                # followed runs is walked, the runs' entries are copied from the walked entries of the stretch they repeat
+                copy_kernels = ("PathWalkFunctor", "RunOutFunctor", "GapOutFunctor", "WalkCompactFunctor", "RunRangeFunctor", "RunFilterFunctor",
+                                "RunGatherFunctor", "RunCompactFunctor", "GapWalkersFunctor", "WalkerRangeFunctor", "SegCountFunctor", "WlinkFlagFunctor",
+                                "WalkInfoFunctor", "MaybeDestFunctor", "PathOffCopyFunctor", "PathEndsFunctor")
+                walked = st["path_entries_walked"]
+                n_steps = 28      # ~24 dependent launches + 4 read-backs in the stage (profiles/r09e_timeline_path_copy_rows.txt)
+                others.append(roof("copying path walk: PathWalkFunctor<W> over the gaps + RunOutFunctor / GapOutFunctor + run bookkeeping (stage `paths`)",
+                                   "get_unitig_path_for_sequence (unitig_graph.rs:407-465) for all sequences",
+                                   walk_ms, 8.0 * n_ent + 24.0 * st["path_runs_copied"] + packed_b * (walked / max(n_ent, 1)) + 96.0 * U_now,
+                                   "every path entry read once from the walked entries and written once (2 x 4 B) + 24 B per copied run + the walked share of "
+                                   "the packed text read once + the unitig / successor records (96 B per unitig) read once",
+                                   sum(pmc_of(nm) or 0 for nm in copy_kernels) or None,
+                                   {"name": "dependent_launches", "operations": n_steps, "bound_ms": n_steps * 0.010, "frac": n_steps * 0.010 / walk_ms if walk_ms else None,
+                                    "note": "kernels and host read-backs that must follow one another (scan -> size -> launch), ~10 us each: the stage's floor once "
+                                            "its per-entry work is streaming copies; %d of %d entries were walked, the rest copied" % (walked, n_ent)}))
+            else:
+                others.append(roof("PathWalkFunctor<W> + PathCompactFunctor (stage `paths`)", "get_unitig_path_for_sequence (unitig_graph.rs:407-465) for all sequences",
+                                   walk_ms, 8.0 * n_ent + packed_b + 96.0 * U_now,
+                                   "every path entry written to its staging slot and once more in text order (2 x 4 B) + the packed text read once + the unitig / "
+                                   "successor records (96 B per unitig) read once",
+                                   (pmc_of("PathWalkFunctor") or 0) + (pmc_of("PathCompactFunctor") or 0) or None, walk_ceiling))
+            exp_ms = stage["expand"] * 1e3
+            n_cand = st["n_candidates"]
+            n_launch = st["n_levels"] * st["simplify_passes"]
+            others.append(roof("expand_wave_kernel<W,16> + level scheduling + sequence rewrite (stage `expand`)",
+                               "expand_repeats (graph_simplification.rs:43-86)", exp_ms, n_cand * (120.0 + 5 * 64.0) + 2.0 * graph_info["total_length"],
+                               "per candidate junction once: its link row and five source records (120 B) + one 64-byte line of each source's sequence; the "
+                               "sequences rewritten once after the last pass (read + write)",
+                               pmc_of("expand_wave_kernel"),
+                               {"name": "dependent_launches", "operations": n_launch, "bound_ms": n_launch * 0.010, "frac": n_launch * 0.010 / exp_ms if exp_ms else None,
+                                "note": "levels x passes kernels that must run one after the other (the reference's visiting order), ~10 us each: junction chains, "
+                                        "not bytes, bind this stage"}))
+            line["roofline_other"] = others
+            # The kernels of this path are bound by random accesses into the k-mer table, not by streamed bytes: price them against
+            # the device's measured random-access ceilings as well (a ~20 ms microbenchmark inside the library).
+            if have_ceil:
+                deg_ms = stage["degree"] * 1e3
+                line["random_access"] = {
+                    "cas_ceiling_Gops": cas.value, "read_ceiling_Gops": rd.value, "measured_on_table_slots": ceil_slots,
+                    "insert": {"slot_claims": st["n_local_distinct"] or st["n_distinct"], "kernel_ms": ins_ms,
+                               "claims_only_bound_ms": (st["n_local_distinct"] or st["n_distinct"]) / cas.value / 1e6,
+                               "frac_of_cas_ceiling": (st["n_local_distinct"] or st["n_distinct"]) / cas.value / 1e6 / ins_ms},
+                    "degree": {"stage_ms": deg_ms, "walks_if_every_degree_were_probed": 2 * st["n_distinct"],
+                               "walks_only_bound_ms": 2 * st["n_distinct"] / rd.value / 1e6,
+                               "stage_over_that_bound": deg_ms / (2 * st["n_distinct"] / rd.value / 1e6)},
+                    "note": "bounds count only the unavoidable random accesses: one CAS per distinct k-mer for the insert; for the degree pass "
+                            "the two probe-cluster walks per distinct k-mer it WOULD need if every degree were probed (round 1-2 form) — the "
+                            "single-device pass settles nearly all of them from the sibling bits the insert collects (DESIGN.md section 4, K5) and only "
+                            "probes the rest, which is why the stage can be faster than that bound"}
         if independent is not None:
             line["independent_jobs"] = independent
         if in_library is not None:
@@ -740,7 +821,7 @@ def main():
                                "local_distinct_rank0": tms[-1]["n_local_distinct"]}
         if os.environ.get("BENCH_STAGE_TIMING"):
             line["timed_stage_ms"] = [{kk: round(vv * 1e3, 2) for kk, vv in t.items() if isinstance(vv, float) and vv > 2e-4 and kk != "insert_kernel_ms"} for t in tms]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             a, b2 = args.cpu_sample.split("x")
             sample = cpu_baseline(k, int(a), int(b2))      # timed now, on this box's host cores
             # cpu_baseline.value = what was TIMED IN THIS RUN, on this box's host cores (the figure recorded elsewhere is context, under

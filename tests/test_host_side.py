@@ -4,6 +4,7 @@ import gzip
 import re
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 import emu_lib
@@ -266,7 +267,7 @@ CONTRACT_KEYS = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per
 
 
 def test_bench_line_contract_single_rank_dry_run():
-    j = _bench_dry_run(["--cpu-sample", "2x20000"], env_extra={"BENCH_EMU_ASSUME_DEFAULT": "1"})
+    j = _bench_dry_run(["--full", "--cpu-sample", "2x20000"], env_extra={"BENCH_EMU_ASSUME_DEFAULT": "1"})
     for key in CONTRACT_KEYS + ["cpu_baseline"]:
         assert key in j, key
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["higher_is_better"] is True and j["scaling"] == "weak"
@@ -308,12 +309,12 @@ def test_bench_line_contract_single_rank_dry_run():
     assert j["cold_first_build_ms"] > 0 and "configs[2]" not in j["config"]["workload"]      # 3 x 30 kbp is not a BASELINE configuration
 
 
-def test_bench_line_two_ranks_dry_run():
+def test_bench_line_two_ranks_dry_run(tmp_path):
     # the N > 1 path of bench.py as the driver launches it (torch.distributed.run, one process per rank): ONE mixed-species job
     # sharded over the ranks, then the same ranks as independent jobs; collectives over gloo here, RCCL on the GPU box
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    j = _bench_dry_run(["--gpus", "2"], launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+    j = _bench_dry_run(["--gpus", "2", "--full", "--dump-outputs", str(tmp_path / "out")], launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                                    "--master-port", str(port)))
     for key in CONTRACT_KEYS + ["sharded", "independent_jobs"]:
         assert key in j, key
@@ -321,3 +322,77 @@ def test_bench_line_two_ranks_dry_run():
     assert j["value"] > 0 and j["independent_jobs"]["value"] > 0
     assert j["sharded"]["unitigs"] > 0 and j["sharded"]["fragments"] >= j["sharded"]["fragments_rank0"]
     assert "cpu_baseline" not in j          # rank 0 at N = 1 only
+    # rank 0 dumps the graph it holds (all unitigs and links; the link records run both ways, `links` counts one)
+    summary = np.load(tmp_path / "out" / "summary.npy")
+    assert summary[0] == j["sharded"]["unitigs"] == j["graph"]["unitigs"] and summary[1] >= j["graph"]["links"] > 0
+
+
+def test_bench_plain_run_is_lean_and_its_dump_is_reproducible(tmp_path):
+    """A plain run (no --full) times the headline bracket only and prints the contract's keys; --dump-outputs writes the last timed
+    step's graph as float32 / float64 .npy files, the same in two runs with the same arguments."""
+    runs = [_bench_dry_run(["--dump-outputs", str(tmp_path / f"run{r}")]) for r in range(2)]
+    for j in runs:
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+            assert key in j, key
+        assert j["steps"] == 2 and j["unit"] == "Mbp/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+        assert j["value"] == j["t_hot"]["value"] and j["ms_per_step"] == j["t_hot"]["ms_per_step"] and len(j["step_ms_list"]) == 2
+        # what --full adds is not measured
+        assert j["roofline"] is None and j["hbm_resident"] is None and j["t_e2e"] is None
+        assert "cpu_baseline" not in j and "stages_s" not in j and "gfa_md5" not in j["t_hot"]
+        assert j["untimed_builds_before_the_timed_steps"]["device_entry_steps"] == 0
+    names = sorted(f.name for f in (tmp_path / "run0").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "run1").iterdir())
+    assert {"summary.npy", "unitig_sequence.npy", "unitig_depth.npy", "link_from.npy", "path_entries.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "run0" / name), np.load(tmp_path / "run1" / name)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), name
+        total += (tmp_path / "run0" / name).stat().st_size
+    assert total <= 64_000_000
+    g = runs[0]["graph"]
+    summary = np.load(tmp_path / "run0" / "summary.npy")
+    assert [summary[0], summary[2], summary[4]] == [g["unitigs"], g["total_length"], g["path_entries"]] and summary[1] >= g["links"] > 0
+
+
+def test_dump_outputs_holds_the_graph_and_samples_large_arrays(tmp_path, monkeypatch):
+    """bench.dump_outputs against the per-item accessors: whole arrays below the sample size; above it, a seeded sample of the
+    elements at the indices <name>_index.npy names, the same sample every time."""
+    import bench
+    import parity_util
+    from autocycler_amd import synth
+    k, seqs, fn, hd = 51, [], [], []
+    for i, contigs in enumerate(synth.make_assemblies(3, genome=30_000, plasmid=1_500, seed=7)):
+        for header, seq in contigs:
+            seqs.append(seq.tobytes().decode()); fn.append(f"assembly_{i:04d}.fasta"); hd.append(header)
+    g, _, _ = parity_util.check_case(k, seqs, fn, hd, lib_path=emu_lib.emu_path())
+    U = g.unitig_count
+    unitigs = [g.unitig(i) for i in range(U)]
+    bases = np.frombuffer(b"".join(s for s, _ in unitigs), dtype=np.uint8)
+    links = g.links()
+    paths = [list(g.path(i)) for i in range(len(seqs))]
+    entries = [e for p in paths for e in p]
+    bench.dump_outputs(g, tmp_path / "whole")
+    load = lambda d, n: np.load(tmp_path / d / f"{n}.npy")
+    assert not list((tmp_path / "whole").glob("*_index.npy"))
+    assert load("whole", "unitig_sequence").dtype == np.float32 and np.array_equal(load("whole", "unitig_sequence"), bases)
+    assert load("whole", "unitig_length").tolist() == [len(s) for s, _ in unitigs]
+    assert load("whole", "unitig_depth").tolist() == [d for _, d in unitigs]
+    assert [(abs(int(a)), a > 0, abs(int(b)), b > 0) for a, b in zip(load("whole", "link_from"), load("whole", "link_to"))] == links
+    assert load("whole", "path_entries").tolist() == entries
+    assert load("whole", "path_offsets").tolist() == np.cumsum([0] + [len(p) for p in paths]).tolist()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 40)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(g, tmp_path / d)
+    sampled = []
+    for name in ("unitig_sequence", "unitig_length", "unitig_depth", "link_from", "link_to", "path_entries", "path_offsets"):
+        whole = load("whole", name)
+        if len(whole) <= 40:
+            assert np.array_equal(load("s1", name), whole) and not (tmp_path / "s1" / f"{name}_index.npy").exists(), name
+            continue
+        sampled.append(name)
+        idx = load("s1", f"{name}_index").astype(np.int64)
+        assert 0 < len(idx) <= 40 and np.all(np.diff(idx) > 0) and np.array_equal(load("s1", name), whole[idx]), name
+        assert np.array_equal(idx, load("s2", f"{name}_index")) and np.array_equal(load("s1", name), load("s2", name)), name
+    assert {"unitig_sequence", "unitig_length", "link_from", "path_entries"} <= set(sampled)
+    assert np.array_equal(load("s1", "summary"), load("whole", "summary"))
+    g.close()

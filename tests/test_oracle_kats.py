@@ -295,8 +295,9 @@ def test_input_assemblies_yaml_follows_the_struct_declarations(tmp_path):
     input_assembly_details: Vec<InputAssemblyDetails { filename, contigs: Vec<InputContigDetails { name, description, length }> }> } —
     as block-style YAML (metrics.rs:256-260, serde_yaml 0.9: `- ` items at the parent key's indentation, nested mappings indented by
     two).  The oracle's file for the five-file fixture is that, line for line; name / description are the contig header up to / after its
-    first space (sequence.rs:77-83).  Where the reference sources are at hand the field lists are re-read from them."""
-    import re
+    first space (sequence.rs:77-83).  The field lists are also checked against the declarations as recorded in
+    tests/golden/metrics_yaml_fields.json."""
+    import json
     from pathlib import Path
     import boundary_cases as B
     src = tmp_path / "asm"
@@ -308,11 +309,8 @@ def test_input_assemblies_yaml_follows_the_struct_declarations(tmp_path):
     top = ["input_assemblies_count", "input_assemblies_total_contigs", "input_assemblies_total_length", "compressed_unitig_count",
            "compressed_unitig_total_length", "input_assembly_details"]
     detail, contig = ["filename", "contigs"], ["name", "description", "length"]
-    ref = Path("/root/reference/src/metrics.rs")
-    if ref.exists():      # the declarations themselves (build container only)
-        text = ref.read_text()
-        fields = lambda name: re.findall(r"pub (\w+):", re.search(r"pub struct %s \{(.*?)\n\}" % name, text, re.S).group(1))
-        assert fields("InputAssemblyMetrics") == top and fields("InputAssemblyDetails") == detail and fields("InputContigDetails") == contig
+    fields = json.loads((Path(__file__).resolve().parent / "golden" / "metrics_yaml_fields.json").read_text())      # the declarations
+    assert fields["InputAssemblyMetrics"] == top and fields["InputAssemblyDetails"] == detail and fields["InputContigDetails"] == contig
     assert [l.split(":")[0] for l in lines if not l.startswith((" ", "-"))] == top
     assert lines[0] == "input_assemblies_count: 6" and lines[1] == "input_assemblies_total_contigs: 7"
     assert lines[2] == "input_assemblies_total_length: %d" % (75 * 7) and lines[5] == "input_assembly_details:"

@@ -1,13 +1,14 @@
 #!/bin/bash
 # ONE runner for the visits to the MI355X box (round 5: replaces the ~45 one-off tools/gpu_r1*.sh of rounds 3-4, which stay in the history).
 #   gpurun --timeout 3000 -- 'bash tools/gpu_visit.sh TAG step [step ...]'
-# Every step writes under gpurun_out/ with the TAG as prefix; what is to be kept is copied to profiles/ afterwards (README.md there).
+# Every step writes its files with the TAG as prefix (the bench and protocol steps under $BENCH_OUT, default tools/_measure/); what is to be
+# kept is copied to profiles/ afterwards (README.md there).
 # Steps:
 #   smoke             __graft_entry__.smoke()
 #   tests[:EXPR]      pytest -m gpu (optionally -k EXPR)                                   -> TAG_pytest_gpu.log
 #   prims             the hand-written scan / radix sort against std:: + the verifier tests  -> TAG_pytest_prims.log
-#   bench[:WORKLOAD]  bench.py (config C: 20 steps, e2e, cpu baseline; a named workload: 5-10 steps, no e2e)  -> TAG_bench_<workload>.json
-#   protocol[:WL]     bench.py --mode sharded --protocol-always at N = 1 beside the direct dispatch           -> TAG_bench_protocol_n1_*.json
+#   bench[:WORKLOAD]  bench.py --full (config C: 20 steps, e2e, cpu baseline; a named workload: 5-10 steps, no e2e)  -> $BENCH_OUT/TAG_bench_<workload>.json
+#   protocol[:WL]     bench.py --full --mode sharded --protocol-always at N = 1 beside the direct dispatch    -> $BENCH_OUT/TAG_bench_protocol_n1_*.json
 #   ab[:WORKLOAD]     tools/ab_knobs.py base;base or $AB_VARIANTS (torch-free driver: stage table, launches, round trips, md5) -> TAG_ab_<workload>.jsonl
 #   calibrate         FETCH_SIZE / WRITE_SIZE per random access (tools/pmc_calibrate_random.sh)                -> TAG_pmc_calibration_random.json
 #   pmc[:WORKLOAD]    the two PMC passes + pmc_traffic json stamped with the source hash                       -> pmc_traffic[_WORKLOAD].json
@@ -20,6 +21,8 @@ export TMPDIR=/tmp
 TAG=$1; shift
 mkdir -p gpurun_out
 R=$PWD
+BENCH_OUT=${BENCH_OUT:-tools/_measure}      # the bench and protocol steps' JSON lines and stderr
+mkdir -p "$BENCH_OUT"
 summ() { python - "$1" <<'PY'
 import json, sys
 try:
@@ -42,11 +45,11 @@ for STEP in "$@"; do
     tests) if [ -n "$ARG" ]; then timeout 2400 python -m pytest tests -m gpu -x -q -k "$ARG" > gpurun_out/${TAG}_pytest_gpu.log 2>&1; else timeout 2400 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}_pytest_gpu.log 2>&1; fi
            echo "pytest exit $?"; tail -4 gpurun_out/${TAG}_pytest_gpu.log ;;
     prims) timeout 900 python -m pytest tests/test_gpu_boundary.py -x -q -k "primitives or verify" > gpurun_out/${TAG}_pytest_prims.log 2>&1; echo "prims exit $?"; tail -3 gpurun_out/${TAG}_pytest_prims.log ;;
-    bench) if [ -z "$ARG" ]; then timeout 900 python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_configC.json 2> gpurun_out/${TAG}_bench.err; echo "bench exit $?"; summ gpurun_out/${TAG}_bench_configC.json
-           else timeout 1500 python bench.py --workload $ARG --steps 8 --warmup 3 --no-e2e > gpurun_out/${TAG}_bench_${ARG}.json 2>> gpurun_out/${TAG}_bench.err; echo "bench $ARG exit $?"; summ gpurun_out/${TAG}_bench_${ARG}.json; fi ;;
+    bench) if [ -z "$ARG" ]; then timeout 900 python bench.py --full --steps 20 --warmup 5 > $BENCH_OUT/${TAG}_bench_configC.json 2> $BENCH_OUT/${TAG}_bench.err; echo "bench exit $?"; summ $BENCH_OUT/${TAG}_bench_configC.json
+           else timeout 1500 python bench.py --full --workload $ARG --steps 8 --warmup 3 --no-e2e > $BENCH_OUT/${TAG}_bench_${ARG}.json 2>> $BENCH_OUT/${TAG}_bench.err; echo "bench $ARG exit $?"; summ $BENCH_OUT/${TAG}_bench_${ARG}.json; fi ;;
     protocol) WL=""; [ -n "$ARG" ] && WL="--workload $ARG"
-           timeout 600 python bench.py $WL --mode sharded --protocol-always --steps 10 --warmup 3 --no-e2e --no-cpu-baseline --pmc off > gpurun_out/${TAG}_bench_protocol_n1_${ARG:-configC}.json 2>> gpurun_out/${TAG}_bench.err; summ gpurun_out/${TAG}_bench_protocol_n1_${ARG:-configC}.json
-           timeout 600 python bench.py $WL --mode sharded --steps 10 --warmup 3 --no-e2e --no-cpu-baseline --pmc off > gpurun_out/${TAG}_bench_sharded_direct_n1_${ARG:-configC}.json 2>> gpurun_out/${TAG}_bench.err; summ gpurun_out/${TAG}_bench_sharded_direct_n1_${ARG:-configC}.json ;;
+           timeout 600 python bench.py --full $WL --mode sharded --protocol-always --steps 10 --warmup 3 --no-e2e --no-cpu-baseline --pmc off > $BENCH_OUT/${TAG}_bench_protocol_n1_${ARG:-configC}.json 2>> $BENCH_OUT/${TAG}_bench.err; summ $BENCH_OUT/${TAG}_bench_protocol_n1_${ARG:-configC}.json
+           timeout 600 python bench.py --full $WL --mode sharded --steps 10 --warmup 3 --no-e2e --no-cpu-baseline --pmc off > $BENCH_OUT/${TAG}_bench_sharded_direct_n1_${ARG:-configC}.json 2>> $BENCH_OUT/${TAG}_bench.err; summ $BENCH_OUT/${TAG}_bench_sharded_direct_n1_${ARG:-configC}.json ;;
     ab)    WL=""; [ -n "$ARG" ] && WL="--workload $ARG"
            AC_NO_TORCH=1 timeout 600 python tools/ab_knobs.py $WL --steps 12 --variants "${AB_VARIANTS:-base;base}" > gpurun_out/${TAG}_ab_${ARG:-configC}.jsonl 2>> gpurun_out/${TAG}.err
            python - gpurun_out/${TAG}_ab_${ARG:-configC}.jsonl <<'PY'
