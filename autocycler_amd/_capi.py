@@ -52,12 +52,41 @@ class Timings(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TrimSlice(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("status", "begin", "end", "trimmed_length")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TrimResult(C.Structure):
+    _fields_ = [("start_end", TrimSlice), ("hairpin", TrimSlice), ("hairpin_start_trimmed", C.c_uint32), ("hairpin_end_trimmed", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(start_end=self.start_end.as_dict(), hairpin=self.hairpin.as_dict(),
+                    hairpin_start_trimmed=self.hairpin_start_trimmed, hairpin_end_trimmed=self.hairpin_end_trimmed)
+
+
+class TrimSummary(C.Structure):
+    _fields_ = [("size", C.c_uint64), ("c_se", C.c_uint32), ("c_hp", C.c_uint32), ("chosen", C.c_uint32), ("launches", C.c_uint32),
+                ("cells", C.c_uint64), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
+class AlignmentPiece(C.Structure):
+    _fields_ = [("a_unitig", C.c_int32), ("a_index", C.c_uint32), ("b_unitig", C.c_int32), ("b_index", C.c_uint32)]
+
+
+ALIGN_GAP, ALIGN_NONE = 0, 0xFFFFFFFF
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int)      # ac_allreduce_fn
 
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_selftest_primitives", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_selftest_primitives", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -126,6 +155,13 @@ def load_library(path=None):
     lib.ac_shard_query_key_words.argtypes = [C.c_void_p]
     lib.ac_graph_seq_count.restype = C.c_uint32
     lib.ac_graph_seq_count.argtypes = [C.c_void_p]
+    lib.ac_trim_max_unitigs.restype = C.c_uint32
+    lib.ac_trim_max_unitigs.argtypes = []
+    lib.ac_trim_paths.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.c_int, C.POINTER(TrimResult), C.POINTER(TrimSummary)]
+    lib.ac_trim_path_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_int,
+                                        C.POINTER(TrimResult), C.POINTER(TrimSummary)]
+    lib.ac_overlap_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_int,
+                                         C.POINTER(AlignmentPiece), C.POINTER(C.c_uint32)]
     _libs[key] = lib
     return lib
 
@@ -249,6 +285,15 @@ class Graph:
         _check(self._lib, self._lib.ac_pairwise_distances(self._h, C.c_int(device), out))
         return [[out[a * S + b] for b in range(S)] for a in range(S)]
 
+    def trim_paths(self, min_identity=0.75, max_unitigs=5000, device=0):
+        """The compute of `autocycler trim` (ac_trim_paths; the defaults are the reference's --min_identity / --max_unitigs): per sequence
+        the slices [begin, end) of its path that start-end and hairpin trimming keep.  Returns (list of result dicts, summary dict)."""
+        n = self._lib.ac_graph_seq_count(self._h)
+        out = (TrimResult * max(n, 1))()
+        sm = TrimSummary(size=C.sizeof(TrimSummary))
+        _check(self._lib, self._lib.ac_trim_paths(self._h, min_identity, max_unitigs, device, out, C.byref(sm)))
+        return [out[i].as_dict() for i in range(n)], sm.as_dict()
+
     def verify(self, seqs, device=0):
         """ac_verify_graph: the round-trip verifier on the device (decompress identity, check_links, depth, renumber order, statistics).
         seqs: [(padded forward bytes, unpadded length, id)] as for compress_build.  Returns the report as a dict; report["failed"] == 0
@@ -302,6 +347,54 @@ def graph_from_gfa(gfa_text, lib_path=None):
         _check(lib, lib.ac_graph_seq_info(h, C.c_uint32(i), None, None, C.byref(fn), C.byref(hd)))
         fns.append(fn.value.decode()); hds.append(hd.value.decode())
     return g, fns, hds
+
+
+def max_trim_unitigs(lib_path=None):
+    """ac_trim_max_unitigs: the largest min(max_unitigs, path length) the alignment kernels take."""
+    return load_library(lib_path).ac_trim_max_unitigs()
+
+
+def _weights_array(weights):
+    """weights: a sequence (weights[u - 1] = length of unitig u) or a dict {unitig number: length} (absent numbers get no weight slot
+    beyond the largest key; a path that names one of the holes aligns it with weight 0)."""
+    if isinstance(weights, dict):
+        m = max(weights) if weights else 0
+        w = [0] * m
+        for u, x in weights.items():
+            w[u - 1] = x
+        weights = w
+    return (C.c_uint32 * max(len(weights), 1))(*weights), len(weights)
+
+
+def overlap_alignment(path_a, path_b, weights, min_identity, max_unitigs, skip_diagonal, device=0, lib_path=None):
+    """overlap_alignment (trim.rs:366-480) of two paths of signed unitig numbers on the device (ac_overlap_alignment).
+    Returns the pieces as (a_unitig, a_index, b_unitig, b_index) tuples; a gap is (ALIGN_GAP, ALIGN_NONE); [] = no alignment."""
+    lib = load_library(lib_path)
+    if len(path_a) != len(path_b):
+        raise AutocyclerError("the two paths differ in length")
+    n = len(path_a)
+    a = (C.c_int32 * max(n, 1))(*path_a); b = (C.c_int32 * max(n, 1))(*path_b)
+    w, nw = _weights_array(weights)
+    pieces = (AlignmentPiece * max(2 * min(n, max_unitigs), 1))()
+    cnt = C.c_uint32()
+    _check(lib, lib.ac_overlap_alignment(a, b, n, w, nw, min_identity, max_unitigs, 1 if skip_diagonal else 0, device, pieces, C.byref(cnt)))
+    return [(pieces[i].a_unitig, pieces[i].a_index, pieces[i].b_unitig, pieces[i].b_index) for i in range(cnt.value)]
+
+
+def trim_path_slices(paths, weights, min_identity=0.75, max_unitigs=5000, device=0, lib_path=None):
+    """ac_trim_path_slices: Graph.trim_paths on caller-supplied paths (lists of signed unitig numbers).  Returns (results, summary)."""
+    lib = load_library(lib_path)
+    flat = [x for p in paths for x in p]
+    off = [0]
+    for p in paths:
+        off.append(off[-1] + len(p))
+    ent = (C.c_int32 * max(len(flat), 1))(*flat)
+    offs = (C.c_uint64 * len(off))(*off)
+    w, nw = _weights_array(weights)
+    out = (TrimResult * max(len(paths), 1))()
+    sm = TrimSummary(size=C.sizeof(TrimSummary))
+    _check(lib, lib.ac_trim_path_slices(ent, offs, len(paths), w, nw, min_identity, max_unitigs, device, out, C.byref(sm)))
+    return [out[i].as_dict() for i in range(len(paths))], sm.as_dict()
 
 
 class VerifyReport(C.Structure):

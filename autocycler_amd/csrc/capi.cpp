@@ -675,6 +675,79 @@ int ac_pairwise_distances(const ac_graph* g, int device, double* out) {
     });
 }
 
+// ---- `autocycler trim`: the path-overlap alignments on the device (kernels_trim.inc), their post-processing on the host (trim_host.cpp) ----
+static void check_min_identity(double min_identity) {
+    if (!(min_identity >= 0.0 && min_identity <= 1.0)) throw DeviceError("min_identity must be between 0 and 1");
+}
+static void trim_slices(const int32_t* path, const uint64_t* off, uint32_t n_seqs, const uint32_t* weights, uint32_t n_weights, double min_identity,
+                        uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    if (!out || (n_seqs && (!path || !off)) || !weights) throw DeviceError("null pointer");
+    check_min_identity(min_identity);
+    if (summary && summary->size < sizeof(uint64_t)) throw DeviceError("ac_trim_summary.size must hold the caller's sizeof(ac_trim_summary)");
+    for (uint32_t s = 0; s < n_seqs; s++) {
+        if (off[s + 1] < off[s] || off[s + 1] - off[s] > 0xFFFFFFFFull) throw DeviceError("path offsets must ascend");
+        validate_trim_path(path + off[s], off[s + 1] - off[s], weights, n_weights, ("path of sequence " + std::to_string(s + 1)).c_str());
+    }
+    std::lock_guard<std::mutex> lock(g_build_mutex);
+    if (g_live_shards) throw DeviceError("a sharded build is in flight in this process");
+    select_device(device);
+    TrimDeviceStats st;
+    std::vector<TrimResult> res(n_seqs);
+    TrimSummary sm;
+    trim_paths_host(path, off, n_seqs, weights, min_identity, max_unitigs,
+                    [&](const std::vector<AlignJob>& jobs, std::vector<AlignOut>& outs) { overlap_alignment_batch(jobs, weights, max_unitigs, &outs, &st); },
+                    res.data(), &sm);
+    for (uint32_t s = 0; s < n_seqs; s++) {
+        const TrimResult& r = res[s];
+        out[s].start_end = ac_trim_slice{r.se.status, r.se.begin, r.se.end, r.se.length};
+        out[s].hairpin = ac_trim_slice{r.hp.status, r.hp.begin, r.hp.end, r.hp.length};
+        out[s].hairpin_start_trimmed = r.hp_start; out[s].hairpin_end_trimmed = r.hp_end;
+    }
+    if (summary) {
+        ac_trim_summary full;
+        memset(&full, 0, sizeof full);
+        full.size = sizeof full; full.c_se = sm.c_se; full.c_hp = sm.c_hp; full.chosen = sm.chosen; full.launches = st.launches;
+        full.cells = st.cells; full.seconds_device = st.seconds_device;
+        const size_t take = std::min<size_t>((size_t)summary->size, sizeof full);
+        memcpy(summary, &full, take);
+    }
+}
+int ac_trim_path_slices(const int32_t* path_entries, const uint64_t* path_off, uint32_t n_seqs, const uint32_t* weights, uint32_t n_weights,
+                        double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    return guarded([&] { trim_slices(path_entries, path_off, n_seqs, weights, n_weights, min_identity, max_unitigs, device, out, summary); });
+}
+int ac_trim_paths(const ac_graph* g, double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    return guarded([&] {
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+        if (n_seqs == 0 || g->g.path_off.size() != (size_t)n_seqs + 1 || !g->g.seq_len) throw DeviceError("trim: the graph holds no paths");
+        trim_slices(g->g.path, g->g.path_off.data(), n_seqs, g->g.seq_len, g->g.n_unitigs, min_identity, max_unitigs, device, out, summary);
+    });
+}
+int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const uint32_t* weights, uint32_t n_weights, double min_identity,
+                         uint32_t max_unitigs, int skip_diagonal, int device, ac_alignment_piece* pieces, uint32_t* n_pieces) {
+    return guarded([&] {
+        if ((n && (!a || !b)) || !weights || !n_pieces || (n && max_unitigs && !pieces)) throw DeviceError("null pointer");
+        check_min_identity(min_identity);
+        validate_trim_path(a, n, weights, n_weights, "path a");
+        validate_trim_path(b, n, weights, n_weights, "path b");
+        *n_pieces = 0;
+        std::lock_guard<std::mutex> lock(g_build_mutex);
+        if (g_live_shards) throw DeviceError("a sharded build is in flight in this process");
+        select_device(device);
+        std::vector<AlignJob> jobs(1);
+        jobs[0].a.assign(a, a + n); jobs[0].b.assign(b, b + n); jobs[0].skip_diagonal = skip_diagonal != 0;
+        std::vector<AlignOut> outs;
+        overlap_alignment_batch(jobs, weights, max_unitigs, &outs, nullptr);
+        if (!alignment_passes(&outs[0], min_identity)) return;
+        static_assert(sizeof(ac_alignment_piece) == sizeof(AlignPiece), "the piece layouts must agree");
+        memcpy(pieces, outs[0].pieces.data(), outs[0].pieces.size() * sizeof(AlignPiece));
+        *n_pieces = (uint32_t)outs[0].pieces.size();
+    });
+}
+uint32_t ac_trim_max_unitigs(void) { return trim_max_unitigs(); }
+
 // UnitigGraph::from_gfa_lines (unitig_graph.rs:55-174) for the GFAs `compress` writes: what `cluster` and `decompress` start from.
 int ac_graph_from_gfa(const char* gfa_text, uint64_t len, ac_graph** out) {
     return guarded([&] {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "graph_types.hpp"
+#include "trim_host.hpp"
 
 namespace ac {
 
@@ -179,6 +180,11 @@ void verify_graph_device(const FinalGraph& g, const uint8_t* d_text, uint64_t n_
 
 // reconstruct_original_sequences (unitig_graph.rs:362-400) for ALL sequences on the device: out_host holds sum(seq_len) bytes, sequence s behind s - 1.
 void decompress_device(const FinalGraph& g, const std::vector<uint32_t>& seq_len, uint8_t* out_host);
+// overlap_alignment (trim.rs:366-480) for a batch of jobs on the device (kernels_trim.inc); the host side of `trim` is trim_host.cpp.
+struct TrimDeviceStats { double seconds_device = 0; uint64_t cells = 0; uint32_t jobs = 0, launches = 0; };
+void overlap_alignment_batch(const std::vector<AlignJob>& jobs, const uint32_t* weights, uint32_t max_unitigs, std::vector<AlignOut>* outs,
+                             TrimDeviceStats* st);
+uint32_t trim_max_unitigs();      // largest min(max_unitigs, path length) the alignment kernels take
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 

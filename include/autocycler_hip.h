@@ -301,6 +301,44 @@ int ac_end_repair_device(uint32_t k, void* d_text, uint64_t n_text, const uint64
  * S = ac_graph_seq_count(), sequences in input order. */
 int ac_pairwise_distances(const ac_graph*, int device, double* out);
 
+/* The compute of `autocycler trim` (trim.rs:45-47: trim_start_end_overlap :104-136, trim_harpin_overlap :139-186, the counts of
+ * choose_trim_type :189-211) on the paths of a graph handle (a build, or ac_graph_from_gfa): overlap_alignment (trim.rs:366-480), a
+ * (k + 1)^2 dynamic programme per sequence and kind with k = min(max_unitigs, path length), runs on the device for all sequences at once
+ * (exact: int64 of the doubled f64 scores; one traceback bit per cell instead of the score matrix).  max_unitigs = 0 disables trimming as
+ * in the reference; min(max_unitigs, path length) above ac_trim_max_unitigs() is an error, never a silent cap.
+ * A result is the slice [begin, end) of the sequence's own path (ac_path) that survives and its length in bases:
+ *   start_end: trim_path_start_end (trim.rs:288-296, find_midpoint :482-507);
+ *   hairpin:   trim_path_hairpin_start (:320-326), then trim_path_hairpin_end (:299-317) on the start-trimmed path (:152-164);
+ *              hairpin_start_trimmed / hairpin_end_trimmed say which of the two fired (the reference's message, :171-177).
+ * status: 0 = not trimmed (the slice is the whole path), 1 = trimmed, 2 = the reference itself would have stopped on this input (the
+ * assertion of trim.rs:310, or a path[start..end] that cannot be taken): reported, not guessed at; such a sequence counts as not trimmed.
+ * Not done here (the caller applies the chosen slices): remove_sequence_from_graph, create_sequence_and_positions, clean_up_graph. */
+typedef struct { uint32_t status, begin, end, trimmed_length; } ac_trim_slice;
+typedef struct { ac_trim_slice start_end, hairpin; uint32_t hairpin_start_trimmed, hairpin_end_trimmed; } ac_trim_result;
+typedef struct {
+    uint64_t size;            /* in: sizeof the caller's ac_trim_summary (at most that many bytes are written); out: the library's */
+    uint32_t c_se, c_hp;      /* sequences trimmed by start-end / by hairpin trimming */
+    uint32_t chosen;          /* choose_trim_type: 0 = none, 1 = the start-end results, 2 = the hairpin results */
+    uint32_t launches;        /* launches of the fill kernel (more than 2 when a phase ran in batches) */
+    uint64_t cells;           /* matrix cells filled */
+    double seconds_device;    /* the alignment kernels, by device events */
+} ac_trim_summary;
+int ac_trim_paths(const ac_graph*, double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out /* ac_graph_seq_count() */,
+                  ac_trim_summary* summary /* may be NULL */);
+/* The same on caller-supplied paths: path_entries[path_off[s] .. path_off[s + 1]) signed unitig numbers, weights[u - 1] = length of unitig u. */
+int ac_trim_path_slices(const int32_t* path_entries, const uint64_t* path_off, uint32_t n_seqs, const uint32_t* weights, uint32_t n_weights,
+                        double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary);
+/* overlap_alignment (trim.rs:366-480) itself, one job through the same kernels: a, b of n entries each, weights[u - 1] = w(u).  pieces
+ * holds 2 * min(n, max_unitigs) entries; *n_pieces = 0: no alignment.  A gap is unitig AC_ALIGN_GAP with index AC_ALIGN_NONE.
+ * Errors (return 1, ac_last_error), never aborts: min_identity outside [0, 1], an entry that is 0 or beyond the weights, the weights of
+ * one path adding up to 2^32 or more, min(n, max_unitigs) above ac_trim_max_unitigs(). */
+#define AC_ALIGN_GAP 0
+#define AC_ALIGN_NONE 0xFFFFFFFFu
+typedef struct { int32_t a_unitig; uint32_t a_index; int32_t b_unitig; uint32_t b_index; } ac_alignment_piece;
+int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const uint32_t* weights, uint32_t n_weights, double min_identity,
+                         uint32_t max_unitigs, int skip_diagonal, int device, ac_alignment_piece* pieces, uint32_t* n_pieces);
+uint32_t ac_trim_max_unitigs(void);   /* 65536: the bit matrix of one alignment is then 537 MB */
+
 /* The loader side of save_gfa for the GFAs `compress` writes (UnitigGraph::from_gfa_lines, unitig_graph.rs:55-174): what
  * `autocycler cluster` (cluster.rs:42-43) and `autocycler decompress` (decompress.rs:27-39) start from.  The handle then serves
  * every accessor above (ac_gfa_string on it reproduces the file: tests.rs:108-112), ac_pairwise_distances and: */
