@@ -1,8 +1,9 @@
 // Device graph build (see graph_build.hpp).  gfx950 HIP; the same file compiles as the CPU emulation
 // under -DAC_EMU for the CPU test-suite.
 //
-// (The shared types, kernels and GraphBuilder::Impl: graph_impl.hpp; the stages per key width: graph_stages.hip; the host entry:
-// graph_upload.hip; the phases of a build over several devices: graph_shard.hip; end repair, distances, verifier: graph_extras.hip.)
+// (The shared types, kernels and GraphBuilder::Impl: graph_impl.hpp; the stages per key width: graph_stages.hip; the order-sensitive
+// tail, which has no key in it: graph_tail.hip; the host entry: graph_upload.hip; the phases of a build over several devices:
+// graph_shard.hip; end repair, distances, verifier: graph_extras.hip.)
 #ifdef AC_EMU
 #define AC_EMU_DEFINE_CTX_SWITCH      // (the lockstep emulation's context switch is defined by this translation unit: wave_rt.hpp)
 #endif
@@ -77,8 +78,9 @@ void device_warmup(int device, uint32_t k, uint64_t text_bytes_estimate) {
             case 1: Stages<1>::warm(); break; case 2: Stages<2>::warm(); break; case 3: Stages<3>::warm(); break;
             case 4: Stages<4>::warm(); break; case 8: Stages<8>::warm(); break; case 16: Stages<16>::warm(); break;
         }
+        tail_warm();      // (... and the tail's, which is no width's: graph_tail.hip)
         (void)hipDeviceSynchronize();
-        lap("key-width code object");
+        lap("key-width + tail code objects");
     }
     if (text_bytes_estimate) {
         Arena::device().reserve(arena_estimate(text_bytes_estimate, true));
@@ -148,7 +150,7 @@ void GraphBuilder::build(uint32_t assembly_count_hint, FinalGraph* out) {
             AC_DISPATCH_W(degrees, (*impl_))
             AC_DISPATCH_W(unitigs, (*impl_))
             AC_DISPATCH_W(walk, (*impl_))
-            AC_DISPATCH_W(tail, (*impl_, out, true, true))
+            m.tail(out, true, true);
             break;
         } catch (const NeedCheckedSorts&) {
             // a deferred "group too large" flag was set (many unitigs sharing a key prefix): once more, every sort checked where it runs

@@ -1,9 +1,9 @@
 // Everything the translation units of the device graph build share (graph_build.hpp is the interface): the table and text types, the
 // kernels (kernels_*.inc), the tuning knobs, PackedText and GraphBuilder::Impl — the device state of one build — and the per-width
 // stage dispatch.  Included by graph_build.hip (builder, single-device driver), graph_stages.hip (the width-dependent stages: compiled
-// once per key width), graph_upload.hip (host entry: packers, upload, path renumbering), graph_shard.hip (the phases of a build
-// over several devices) and graph_extras.hip (end repair, pairwise distances, verifier).  gfx950 HIP; under -DAC_EMU the same sources
-// compile as the CPU emulation for the CPU test-suite.
+// once per key width), graph_tail.hip (the order-sensitive tail, K12..K17: no key in it, compiled once), graph_upload.hip (host entry:
+// packers, upload, path renumbering), graph_shard.hip (the phases of a build over several devices) and graph_extras.hip (end repair,
+// pairwise distances, verifier).  gfx950 HIP; under -DAC_EMU the same sources compile as the CPU emulation for the CPU test-suite.
 //
 // Order-free formulation (derived from unitig_graph.rs:176-226):
 //   * one canonical key per strand pair, stored in an open-addressing table whose slot holds the text
@@ -50,9 +50,9 @@ static const int MAX_PROBES = 1 << 14;
 // diversity.  It raises the error word; every wavefront polls that word and stops, and the host retries with a table four times
 // the size.  (Without the early stop a full table turns every insert into a scan of MAX_PROBES slots: minutes instead of ms.)
 static const int MAX_PROBES_INSERT = 1 << 10;
-// This file is compiled once per key width (-DAC_W_ONLY=1,2,3,4,8,16: the kernels and the stage code of that width only) and
-// once as the main unit (AC_W_ONLY=0: everything that does not depend on the width, and the dispatch), so that the widths
-// build in parallel.  The CPU emulation compiles it once with everything in.
+// This file is compiled once per key width (graph_stages.hip with -DAC_W_ONLY=1,2,3,4,8,16: the kernels and the stage code of that
+// width only) and once in each of the other units (AC_W_ONLY=0: everything that does not depend on the width — the tail, graph_tail.hip,
+// among it — and the dispatch), so that the widths build in parallel.  The CPU emulation compiles graph_stages.hip once with every width in.
 #ifndef AC_W_ONLY
 #define AC_W_ONLY 0
 #endif
@@ -788,7 +788,7 @@ struct GraphBuilder::Impl {
     template <int W> void walk();
     template <int W> bool walk_copy_prepare(u32 PC, const Novel& nv_text);   // K10c, first half: false = not worth it (or not possible) for this text, nothing kept
     template <int W> void walk_copy_finish(u32 PC);                          // K10c, second half: the walk over the gaps and the copies
-    template <int W> void tail(FinalGraph* out, bool want_graph, bool want_paths);
+    void tail(FinalGraph* out, bool want_graph, bool want_paths);      // K12..K17 + D2H: no key in it, compiled once (graph_tail.hip)
     // sharded builds: in-place all-reduce of a device buffer over the ranks (dtype 0 = uint8, 1 = int32; op 0 = SUM, 1 = MIN), given by
     // whoever drives the ranks.  With it the tail runs expand_repeats on this rank's share of the junctions only (conflict components,
     // kernels_tail.inc) and merges the sequences; without it every rank runs all of them.
@@ -863,10 +863,11 @@ template <int W> struct Stages {
     static void route_queries(GraphBuilder::Impl& m, u32 n_shards, u64* d_routed_keys, u64* counts_host);
     static void unitigs(GraphBuilder::Impl& m);
     static void walk(GraphBuilder::Impl& m);
-    static void tail(GraphBuilder::Impl& m, FinalGraph* out, bool want_graph, bool want_paths);
     static void fragments(GraphBuilder::Impl& m);
     static void warm();      // loads this width's code object (an empty launch of its insert kernel)
 };
+
+void tail_warm();      // loads the tail's code object (graph_tail.hip: an empty launch of its expand kernel)
 
 #define AC_DISPATCH_W(NAME, ARGS)                                        \
     switch (key_words((int)impl_->k)) {                                  \

@@ -229,7 +229,7 @@ void GraphBuilder::shard_finish(FinalGraph* out, bool want_graph, bool want_path
     // a rank that keeps the paths of its own sequences lets the host give them their final numbers, like a single-device build (round 5:
     // PathRemapJob — the entries cross PCIe under the tail instead of behind it); the device copy then stays in seed numbers
     impl_->host_remap_allowed = want_paths && shard_host_remap();
-    AC_DISPATCH_W(tail, (*impl_, out, want_graph, want_paths))
+    impl_->tail(out, want_graph, want_paths);
 }
 uint64_t GraphBuilder::path_entry_count() const { return impl_->n_ent; }
 void GraphBuilder::paths_export(void* d_out) {

@@ -535,7 +535,7 @@ template <int G, bool SPARSE> AC_D void expand_junction(const ExpState& e, const
         }
     }
 }
-template <int W, int G> AC_KERNEL void __launch_bounds__(256) expand_wave_kernel(ExpState e, const u32* clist, u64 begin, u64 count, u32 pool_cap, u32* err) {
+template <int G> AC_KERNEL void __launch_bounds__(256) expand_wave_kernel(ExpState e, const u32* clist, u64 begin, u64 count, u32 pool_cap, u32* err) {
     // G lanes per junction (64, or 16: four junctions per wavefront — most shifts are a few dozen characters, and a level's time is
     // its number of wavefronts / the resident ones x one junction's dependency chain).  `lane` = lane within the group; ballots are
     // cut down to the group's bits, shuffles read the group's first lane; everything that branches does so per group.
@@ -586,7 +586,7 @@ struct MopCompactFunctor {      // launch_full over the candidates (in level ord
 struct MopState { u64* list; u32* n; const u32* prio; const u32* level; const u64* sh_words; u32* out; u32 max_start, max_list, sub_limit, batch; };      // batch <= MOP_BATCH (smaller in tests: the straight-from-the-list branch)
 // out[0]: 0 = did not run (list too long, or the passes before it had already finished), 1 = ran to the fixed point, 2 = stopped at a sweep
 // boundary (the host loop goes on); out[1]: sweeps = passes of the reference (the last one of status 1 moved nothing); out[2]: the list at its start
-template <int W> AC_KERNEL void __launch_bounds__(512) expand_mopup_kernel(ExpState e, MopState m, u32 pool_cap, u32* err) {
+template <int UNUSED> AC_KERNEL void __launch_bounds__(512) expand_mopup_kernel(ExpState e, MopState m, u32 pool_cap, u32* err) {      // (a template only so that every translation unit may hold a copy)
     AC_SHARED u32 s_batch[MOP_BATCH];
     AC_SHARED u32 s_cnt, s_next, s_moved, s_stop, s_run;
     const u32 tid = wv::tid();

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch / occupancy of every kernel of graph_build.hip for the W=2 (k=51) instantiations:
-    hipcc ... -Rpass-analysis=kernel-resource-usage -c graph_build.hip 2> res.txt ; python tools/kernel_resources.py res.txt"""
+"""VGPRs / scratch / occupancy of every kernel of one translation unit of csrc/ -- graph_stages.hip for the kernels of a key width
+(-DAC_W_ONLY=2: k=51), graph_tail.hip for those of the tail (no width):
+    hipcc ... -Rpass-analysis=kernel-resource-usage -DAC_W_ONLY=2 -c graph_stages.hip 2> res.txt ; python tools/kernel_resources.py res.txt"""
 import re
 import subprocess
 import sys
