@@ -81,12 +81,26 @@ class AlignmentPiece(C.Structure):
 
 ALIGN_GAP, ALIGN_NONE = 0, 0xFFFFFFFF
 
+
+class DepthGraph(C.Structure):      # ac_depth_graph
+    _fields_ = [("seq_bytes", C.c_void_p), ("seq_begin", C.c_void_p), ("seq_len", C.c_void_p), ("n_unitigs", C.c_uint32),
+                ("links", C.c_void_p), ("n_links", C.c_uint64)]
+
+
+class DepthTotals(C.Structure):
+    _fields_ = [("size", C.c_uint64)] + \
+               [(n, C.c_uint64) for n in ("reads", "rejected_reads", "read_bases", "span_bases", "span_kmers", "hits", "distinct_kmers", "repeat_kmers",
+                                          "table_slots")] + [("batches", C.c_uint32), ("launches", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int)      # ac_allreduce_fn
 
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_selftest_primitives", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -162,6 +176,15 @@ def load_library(path=None):
                                         C.POINTER(TrimResult), C.POINTER(TrimSummary)]
     lib.ac_overlap_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_int,
                                          C.POINTER(AlignmentPiece), C.POINTER(C.c_uint32)]
+    lib.ac_depth_begin.argtypes = [C.c_uint32, C.POINTER(DepthGraph), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_depth_begin_handles.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_depth_add_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.ac_depth_add_fastq.argtypes = [C.c_void_p, C.c_char_p]
+    lib.ac_depth_totals_get.argtypes = [C.c_void_p, C.POINTER(DepthTotals)]
+    lib.ac_depth_kmer_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ac_depth_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ac_depth_free.argtypes = [C.c_void_p]
+    lib.ac_depth_free.restype = None
     _libs[key] = lib
     return lib
 
@@ -395,6 +418,104 @@ def trim_path_slices(paths, weights, min_identity=0.75, max_unitigs=5000, device
     sm = TrimSummary(size=C.sizeof(TrimSummary))
     _check(lib, lib.ac_trim_path_slices(ent, offs, len(paths), w, nw, min_identity, max_unitigs, device, out, C.byref(sm)))
     return [out[i].as_dict() for i in range(len(paths))], sm.as_dict()
+
+
+class ReadDepth:
+    """Read-based unitig depths (set_read_depths, depth.rs:45-76) on the device: ac_depth_*.
+
+    graphs: one entry per consensus graph, either a Graph handle or a pair (unitig sequences as bytes, links as (a, b) pairs of signed
+    unitig numbers in L-line order, both directions present).  All graphs share one k-mer table."""
+
+    def __init__(self, k, graphs, device=0, lib_path=None):
+        self._lib = lib = load_library(lib_path)
+        self._h = C.c_void_p()
+        graphs = list(graphs)
+        self.n_unitigs = []
+        if graphs and all(isinstance(g, Graph) for g in graphs):
+            hs = (C.c_void_p * len(graphs))(*[g._h for g in graphs])
+            self.n_unitigs = [lib.ac_unitig_count(g._h) for g in graphs]
+            _check(lib, lib.ac_depth_begin_handles(C.c_uint32(k), hs, C.c_uint32(len(graphs)), C.c_int(device), C.byref(self._h)))
+            return
+        arr = (DepthGraph * max(len(graphs), 1))()
+        keep = []
+        for i, (seqs, links) in enumerate(graphs):
+            seqs = [bytes(s) for s in seqs]
+            blob = b"".join(seqs)
+            begin, at = [], 0
+            for s in seqs:
+                begin.append(at); at += len(s)
+            n = len(seqs)
+            c_blob = C.create_string_buffer(blob, max(len(blob), 1))
+            c_begin = (C.c_uint64 * max(n, 1))(*begin)
+            c_len = (C.c_uint32 * max(n, 1))(*[len(s) for s in seqs])
+            c_links = (Link * max(len(links), 1))(*[Link(a, b) for a, b in links])
+            keep.append((c_blob, c_begin, c_len, c_links))
+            arr[i].seq_bytes, arr[i].seq_begin, arr[i].seq_len = C.addressof(c_blob), C.addressof(c_begin), C.addressof(c_len)
+            arr[i].n_unitigs, arr[i].links, arr[i].n_links = n, C.addressof(c_links), len(links)
+            self.n_unitigs.append(n)
+        _check(lib, lib.ac_depth_begin(C.c_uint32(k), arr, C.c_uint32(len(graphs)), C.c_int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.ac_depth_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add_reads(self, reads):
+        """reads: a list of bytes objects (one read each)."""
+        reads = [bytes(r) for r in reads]
+        blob = b"".join(reads)
+        off, at = [0], 0
+        for r in reads:
+            at += len(r); off.append(at)
+        self.add_reads_raw(blob, off)
+
+    def add_reads_raw(self, bases, read_off):
+        """bases: bytes or a C-contiguous uint8 numpy array; read_off: len(reads) + 1 ascending offsets into it."""
+        n = len(read_off) - 1
+        if hasattr(read_off, "ctypes"):
+            import numpy as np
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+            c_off = read_off.ctypes.data_as(C.c_void_p)
+        else:
+            c_off = (C.c_uint64 * (n + 1))(*read_off)
+        c_bases = bases.ctypes.data_as(C.c_void_p) if hasattr(bases, "ctypes") else C.cast(C.c_char_p(bases), C.c_void_p)
+        _check(self._lib, self._lib.ac_depth_add_reads(self._h, c_bases, c_off, C.c_uint64(n)))
+
+    def add_fastq(self, path):
+        _check(self._lib, self._lib.ac_depth_add_fastq(self._h, os.fsencode(str(path))))
+
+    def totals(self):
+        t = DepthTotals(size=C.sizeof(DepthTotals))
+        _check(self._lib, self._lib.ac_depth_totals_get(self._h, C.byref(t)))
+        return t.as_dict()
+
+    def kmer_counts(self, kmers):
+        """canonical k-mer values -> (present, assembly_occurrences, read_count), three lists."""
+        kmers = list(kmers)
+        n = len(kmers)
+        q = (C.c_uint64 * max(n, 1))(*kmers)
+        present = (C.c_uint8 * max(n, 1))(); occ = (C.c_uint32 * max(n, 1))(); cnt = (C.c_uint32 * max(n, 1))()
+        _check(self._lib, self._lib.ac_depth_kmer_counts(self._h, q, C.c_uint64(n), present, occ, cnt))
+        return list(present)[:n], list(occ)[:n], list(cnt)[:n]
+
+    def depths(self, graph_index):
+        """-> one entry per unitig of that graph: its read depth (float), or None where the reference leaves it without one."""
+        n = self.n_unitigs[graph_index] if 0 <= graph_index < len(self.n_unitigs) else 0
+        depth = (C.c_double * max(n, 1))(); has = (C.c_uint8 * max(n, 1))()
+        _check(self._lib, self._lib.ac_depth_finish(self._h, C.c_uint32(graph_index), depth, has))
+        return [depth[i] if has[i] else None for i in range(n)]
 
 
 class VerifyReport(C.Structure):

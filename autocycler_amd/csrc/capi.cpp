@@ -25,6 +25,7 @@
 #include <unistd.h>
 #include "device_rt.hpp"
 #include "multi_build.hpp"
+#include "graph_depth.hpp"
 
 using namespace ac;
 
@@ -747,6 +748,116 @@ int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const u
     });
 }
 uint32_t ac_trim_max_unitigs(void) { return trim_max_unitigs(); }
+
+// ---- read-based unitig depths of `autocycler combine --reads` (depth.rs:45-76): the k-mer table and the read tally on the device
+// (graph_depth.hip), the graph walks and the per-unitig arithmetic on the host (depth_host.cpp) ----
+struct ac_depth {
+    int device = 0;
+    std::unique_ptr<DepthEngine> e;
+};
+// every call on a handle: one device user at a time per process, the handle's own device current
+struct DepthCall {
+    std::lock_guard<std::mutex> lock;
+    explicit DepthCall(int device) : lock(g_build_mutex) {
+        if (g_live_shards) throw DeviceError("a sharded build is in flight in this process");
+        select_device(device);
+    }
+};
+static void depth_begin(uint32_t k, const ac_depth_graph* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    if (!out || (n_graphs && !graphs)) throw DeviceError("null pointer");
+    *out = nullptr;
+    if (k % 2 == 0 || k < 11 || k > 31) throw DeviceError("--kmer must be an odd number between 11 and 31 (inclusive) for read-based depths");
+    std::vector<DepthGraphView> views(n_graphs);
+    std::vector<DepthGraphPlan> plans(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; g++) {
+        const ac_depth_graph& a = graphs[g];
+        if ((a.n_unitigs && (!a.seq_bytes || !a.seq_begin || !a.seq_len)) || (a.n_links && !a.links)) throw DeviceError("null pointer in graph " + std::to_string(g + 1));
+        static_assert(sizeof(ac_link) == 2 * sizeof(int32_t), "layout");
+        views[g] = DepthGraphView{a.seq_bytes, a.seq_begin, a.seq_len, a.n_unitigs, (const int32_t*)a.links, a.n_links};
+        depth_plan_graph(k, views[g], g, &plans[g]);
+    }
+    auto h = std::make_unique<ac_depth>();
+    h->device = device;
+    DepthCall call(device);
+    h->e = std::make_unique<DepthEngine>(k, views, std::move(plans));      // (a failure on the way frees what the engine already held)
+    *out = h.release();
+}
+int ac_depth_begin(uint32_t k, const ac_depth_graph* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    return guarded([&] { depth_begin(k, graphs, n_graphs, device, out); });
+}
+int ac_depth_begin_handles(uint32_t k, const ac_graph* const* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    return guarded([&] {
+        if (n_graphs && !graphs) throw DeviceError("null pointer");
+        std::vector<ac_depth_graph> a(n_graphs);
+        for (uint32_t g = 0; g < n_graphs; g++) {
+            if (!graphs[g]) throw DeviceError("null pointer");
+            memset(&a[g], 0, sizeof a[g]);
+            if (ac_unitigs_bulk(graphs[g], &a[g].seq_bytes, &a[g].seq_begin, &a[g].seq_len, nullptr) || ac_links(graphs[g], &a[g].links, &a[g].n_links))
+                throw DeviceError(g_err);
+            a[g].n_unitigs = graphs[g]->g.n_unitigs;
+        }
+        depth_begin(k, a.data(), n_graphs, device, out);
+    });
+}
+static void depth_check_offsets(const uint8_t* bases, const uint64_t* read_off, uint64_t n_reads) {
+    if (n_reads && !read_off) throw DeviceError("null pointer");
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (read_off[r + 1] < read_off[r]) throw DeviceError("read_off must ascend (read " + std::to_string(r + 1) + " ends before it starts)");
+    if (n_reads && read_off[n_reads] > read_off[0] && !bases) throw DeviceError("null pointer");
+}
+int ac_depth_add_reads(ac_depth* d, const uint8_t* bases, const uint64_t* read_off, uint64_t n_reads) {
+    return guarded([&] {
+        if (!d) throw DeviceError("null pointer");
+        depth_check_offsets(bases, read_off, n_reads);
+        DepthCall call(d->device);
+        d->e->add_reads(bases, read_off, n_reads);
+    });
+}
+int ac_depth_add_fastq(ac_depth* d, const char* path) {
+    return guarded([&] {
+        if (!d || !path) throw DeviceError("null pointer");
+        depth_read_fastq(path, (size_t)64 << 20, [&](const std::vector<uint8_t>& bases, const std::vector<uint64_t>& off) {
+            DepthCall call(d->device);
+            d->e->add_reads(bases.data(), off.data(), off.size() - 1);
+        });
+    });
+}
+int ac_depth_totals_get(const ac_depth* d, ac_depth_totals* out) {
+    return guarded([&] {
+        if (!d || !out) throw DeviceError("null pointer");
+        if (out->size < sizeof(uint64_t)) throw DeviceError("ac_depth_totals.size must hold the caller's sizeof(ac_depth_totals)");
+        DepthCall call(d->device);
+        const DepthTotals t = d->e->totals();
+        ac_depth_totals full;
+        memset(&full, 0, sizeof full);
+        full.size = sizeof full;
+        full.reads = t.reads; full.rejected_reads = t.rejected_reads; full.read_bases = t.read_bases; full.span_bases = t.span_bases;
+        full.span_kmers = t.span_kmers; full.hits = t.hits; full.distinct_kmers = t.distinct_kmers; full.repeat_kmers = t.repeat_kmers;
+        full.table_slots = t.table_slots; full.batches = t.batches; full.launches = t.launches; full.seconds_device = t.seconds_device;
+        memcpy(out, &full, std::min<size_t>((size_t)out->size, sizeof full));
+    });
+}
+int ac_depth_kmer_counts(ac_depth* d, const uint64_t* kmers, uint64_t n, uint8_t* present, uint32_t* assembly_occurrences, uint32_t* read_count) {
+    return guarded([&] {
+        if (!d || (n && !kmers)) throw DeviceError("null pointer");
+        DepthCall call(d->device);
+        d->e->kmer_counts(kmers, n, present, assembly_occurrences, read_count);
+    });
+}
+int ac_depth_finish(ac_depth* d, uint32_t graph_index, double* depth, uint8_t* has_depth) {
+    return guarded([&] {
+        if (!d) throw DeviceError("null pointer");
+        if (graph_index >= d->e->n_graphs()) throw DeviceError("graph index out of range");
+        if (d->e->n_unitigs(graph_index) && (!depth || !has_depth)) throw DeviceError("null pointer");
+        DepthCall call(d->device);
+        d->e->finish(graph_index, depth, has_depth);
+    });
+}
+void ac_depth_free(ac_depth* d) {
+    if (!d) return;
+    std::lock_guard<std::mutex> lock(g_build_mutex);
+    delete d;
+}
 
 // UnitigGraph::from_gfa_lines (unitig_graph.rs:55-174) for the GFAs `compress` writes: what `cluster` and `decompress` start from.
 int ac_graph_from_gfa(const char* gfa_text, uint64_t len, ac_graph** out) {

@@ -339,6 +339,39 @@ int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const u
                          uint32_t max_unitigs, int skip_diagonal, int device, ac_alignment_piece* pieces, uint32_t* n_pieces);
 uint32_t ac_trim_max_unitigs(void);   /* 65536: the bit matrix of one alignment is then 537 MB */
 
+/* Read-based unitig depths, the --reads step of `autocycler combine` (set_read_depths, depth.rs:45-76; combine.rs:43-46 calls it): a table
+ * of the consensus assembly's canonical k-mers (every k-mer of every unitig's forward sequence plus the k-mers that run across a link,
+ * each occurrence counted; k odd, 11 .. 31) is built on the device, every read is streamed through it in two passes (count_one_read,
+ * depth.rs:394-419: a read with fewer than 0.5 % of its k-mers in the table is left out), and a unitig's depth is the clipped mean of its
+ * non-repeat k-mers' read counts times span_bases / hits (tig_kmer_counts, clipped_mean: sequential f64 on the host, in the reference's
+ * order).  All graphs of a handle share one table: a k-mer is a repeat when it occurs more than once across all of them together.
+ * A graph comes as plain arrays — segments as ac_unitigs_bulk gives them, links in L-line (file) order with both directions present,
+ * signed unitig numbers as ac_link — or, ac_depth_begin_handles, as graph handles (ac_unitigs_bulk + ac_links).  Anything in a sequence or
+ * a read that is not ACGTacgt breaks the run of k-mers.  Reads may be added in any number of calls; device memory per batch of reads is
+ * capped (AC_DEPTH_BATCH_BYTES lowers the cap: tests), a read longer than the cap is a batch of its own.
+ * Errors (return 1, ac_last_error), never aborts: k even or outside 11 .. 31, a link end that is 0 or beyond its graph, a read_off that
+ * does not ascend, a FASTQ that ends inside a record, ac_depth_finish when no read was accepted ("no reads were found ... which match the
+ * consensus assembly", depth.rs:385-391). */
+typedef struct ac_depth ac_depth;
+typedef struct { const uint8_t* seq_bytes; const uint64_t* seq_begin; const uint32_t* seq_len; uint32_t n_unitigs;
+                 const ac_link* links; uint64_t n_links; } ac_depth_graph;
+int ac_depth_begin(uint32_t k, const ac_depth_graph* graphs, uint32_t n_graphs, int device, ac_depth** out);
+int ac_depth_begin_handles(uint32_t k, const ac_graph* const* graphs, uint32_t n_graphs, int device, ac_depth** out);
+int ac_depth_add_reads(ac_depth*, const uint8_t* bases, const uint64_t* read_off /* n_reads + 1 */, uint64_t n_reads);
+int ac_depth_add_fastq(ac_depth*, const char* path);   /* plain or gzip, strict 4-line records; host parsing, then ac_depth_add_reads */
+typedef struct {
+    uint64_t size;            /* in: sizeof the caller's ac_depth_totals (at most that many bytes are written); out: the library's */
+    uint64_t reads, rejected_reads, read_bases, span_bases, span_kmers, hits;   /* ReadTotals, depth.rs:446-453 */
+    uint64_t distinct_kmers, repeat_kmers, table_slots;
+    uint32_t batches, launches;
+    double seconds_device;    /* pass 1 + accept + pass 2 of every batch, by device events */
+} ac_depth_totals;
+int ac_depth_totals_get(const ac_depth*, ac_depth_totals* out);
+/* lookup of canonical k-mer values: present[i], assembly_occurrences[i] (before the reset), read_count[i]; any out pointer may be NULL */
+int ac_depth_kmer_counts(ac_depth*, const uint64_t* kmers, uint64_t n, uint8_t* present, uint32_t* assembly_occurrences, uint32_t* read_count);
+int ac_depth_finish(ac_depth*, uint32_t graph_index, double* depth /* n_unitigs */, uint8_t* has_depth /* 0 = the reference's None */);
+void ac_depth_free(ac_depth*);
+
 /* The loader side of save_gfa for the GFAs `compress` writes (UnitigGraph::from_gfa_lines, unitig_graph.rs:55-174): what
  * `autocycler cluster` (cluster.rs:42-43) and `autocycler decompress` (decompress.rs:27-39) start from.  The handle then serves
  * every accessor above (ac_gfa_string on it reproduces the file: tests.rs:108-112), ac_pairwise_distances and: */
