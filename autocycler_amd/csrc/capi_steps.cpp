@@ -1,0 +1,320 @@
+// C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, read depths, the
+// verifier, decompress, the GFA reload, and the self-tests of the device primitives.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+#include "capi_common.hpp"
+#include "gfa_writer.hpp"
+#include "graph_depth.hpp"
+
+using namespace ac;
+using namespace ac::abi;
+
+extern "C" {
+
+// sequence_end_repair (compress.rs:202-270) on a device-resident text of padded, unrepaired sequences.
+int ac_end_repair_device(uint32_t k, void* d_text, uint64_t n_text, const uint64_t* seq_off, const uint32_t* seq_len,
+                         uint16_t* seq_d1, uint16_t* seq_d2, uint32_t n_seqs, int device, double* seconds, uint64_t* n_matches) {
+    return guarded([&] {
+        if (!d_text || n_seqs == 0) throw DeviceError("no sequences found in input assemblies");
+        if (!seq_d1 || !seq_d2) throw DeviceError("null sequence table");
+        {   // seq_d1 / seq_d2 are outputs here (the repair counts the surviving dots itself): only the layout is checked
+            std::vector<uint16_t> zero(n_seqs, 0);
+            validate_layout(k, n_text, seq_off, seq_len, zero.data(), zero.data(), n_seqs);
+        }
+        DeviceCall call(device);
+        std::vector<uint64_t> off(seq_off, seq_off + n_seqs);
+        std::vector<uint32_t> len(seq_len, seq_len + n_seqs);
+        std::vector<uint16_t> d1(n_seqs, 0), d2(n_seqs, 0);
+        RepairTimings tm;
+        end_repair_device(k, (uint8_t*)d_text, n_text, off, len, &d1, &d2, &tm);
+        for (uint32_t i = 0; i < n_seqs; i++) { seq_d1[i] = d1[i]; seq_d2[i] = d2[i]; }
+        if (seconds) *seconds = tm.total;
+        if (n_matches) *n_matches = tm.matches;
+    });
+}
+
+// pairwise_contig_distances (cluster.rs:132-157), the first step of `autocycler cluster`, on the graph just built.
+int ac_pairwise_distances(const ac_graph* g, int device, double* out) {
+    return guarded([&] {
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        DeviceCall call(device);
+        pairwise_distances_device(g->g, (uint32_t)g->seq_ids.size(), out);
+    });
+}
+
+// ---- `autocycler trim`: the path-overlap alignments on the device (kernels_trim.inc), their post-processing on the host (trim_host.cpp) ----
+static void check_min_identity(double min_identity) {
+    if (!(min_identity >= 0.0 && min_identity <= 1.0)) throw DeviceError("min_identity must be between 0 and 1");
+}
+static void trim_slices(const int32_t* path, const uint64_t* off, uint32_t n_seqs, const uint32_t* weights, uint32_t n_weights, double min_identity,
+                        uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    if (!out || (n_seqs && (!path || !off)) || !weights) throw DeviceError("null pointer");
+    check_min_identity(min_identity);
+    if (summary && summary->size < sizeof(uint64_t)) throw DeviceError("ac_trim_summary.size must hold the caller's sizeof(ac_trim_summary)");
+    for (uint32_t s = 0; s < n_seqs; s++) {
+        if (off[s + 1] < off[s] || off[s + 1] - off[s] > 0xFFFFFFFFull) throw DeviceError("path offsets must ascend");
+        validate_trim_path(path + off[s], off[s + 1] - off[s], weights, n_weights, ("path of sequence " + std::to_string(s + 1)).c_str());
+    }
+    DeviceCall call(device);
+    TrimDeviceStats st;
+    std::vector<TrimResult> res(n_seqs);
+    TrimSummary sm;
+    trim_paths_host(path, off, n_seqs, weights, min_identity, max_unitigs,
+                    [&](const std::vector<AlignJob>& jobs, std::vector<AlignOut>& outs) { overlap_alignment_batch(jobs, weights, max_unitigs, &outs, &st); },
+                    res.data(), &sm);
+    for (uint32_t s = 0; s < n_seqs; s++) {
+        const TrimResult& r = res[s];
+        out[s].start_end = ac_trim_slice{r.se.status, r.se.begin, r.se.end, r.se.length};
+        out[s].hairpin = ac_trim_slice{r.hp.status, r.hp.begin, r.hp.end, r.hp.length};
+        out[s].hairpin_start_trimmed = r.hp_start; out[s].hairpin_end_trimmed = r.hp_end;
+    }
+    if (summary) {
+        ac_trim_summary full;
+        memset(&full, 0, sizeof full);
+        full.size = sizeof full; full.c_se = sm.c_se; full.c_hp = sm.c_hp; full.chosen = sm.chosen; full.launches = st.launches;
+        full.cells = st.cells; full.seconds_device = st.seconds_device;
+        const size_t take = std::min<size_t>((size_t)summary->size, sizeof full);
+        memcpy(summary, &full, take);
+    }
+}
+int ac_trim_path_slices(const int32_t* path_entries, const uint64_t* path_off, uint32_t n_seqs, const uint32_t* weights, uint32_t n_weights,
+                        double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    return guarded([&] { trim_slices(path_entries, path_off, n_seqs, weights, n_weights, min_identity, max_unitigs, device, out, summary); });
+}
+int ac_trim_paths(const ac_graph* g, double min_identity, uint32_t max_unitigs, int device, ac_trim_result* out, ac_trim_summary* summary) {
+    return guarded([&] {
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+        if (n_seqs == 0 || g->g.path_off.size() != (size_t)n_seqs + 1 || !g->g.seq_len) throw DeviceError("trim: the graph holds no paths");
+        trim_slices(g->g.path, g->g.path_off.data(), n_seqs, g->g.seq_len, g->g.n_unitigs, min_identity, max_unitigs, device, out, summary);
+    });
+}
+int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const uint32_t* weights, uint32_t n_weights, double min_identity,
+                         uint32_t max_unitigs, int skip_diagonal, int device, ac_alignment_piece* pieces, uint32_t* n_pieces) {
+    return guarded([&] {
+        if ((n && (!a || !b)) || !weights || !n_pieces || (n && max_unitigs && !pieces)) throw DeviceError("null pointer");
+        check_min_identity(min_identity);
+        validate_trim_path(a, n, weights, n_weights, "path a");
+        validate_trim_path(b, n, weights, n_weights, "path b");
+        *n_pieces = 0;
+        DeviceCall call(device);
+        std::vector<AlignJob> jobs(1);
+        jobs[0].a.assign(a, a + n); jobs[0].b.assign(b, b + n); jobs[0].skip_diagonal = skip_diagonal != 0;
+        std::vector<AlignOut> outs;
+        overlap_alignment_batch(jobs, weights, max_unitigs, &outs, nullptr);
+        if (!alignment_passes(&outs[0], min_identity)) return;
+        static_assert(sizeof(ac_alignment_piece) == sizeof(AlignPiece), "the piece layouts must agree");
+        memcpy(pieces, outs[0].pieces.data(), outs[0].pieces.size() * sizeof(AlignPiece));
+        *n_pieces = (uint32_t)outs[0].pieces.size();
+    });
+}
+uint32_t ac_trim_max_unitigs(void) { return trim_max_unitigs(); }
+
+// ---- read-based unitig depths of `autocycler combine --reads` (depth.rs:45-76): the k-mer table and the read tally on the device
+// (graph_depth.hip), the graph walks and the per-unitig arithmetic on the host (depth_host.cpp) ----
+struct ac_depth {      // (every call on a handle makes the handle's own device current)
+    int device = 0;
+    std::unique_ptr<DepthEngine> e;
+};
+static void depth_begin(uint32_t k, const ac_depth_graph* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    if (!out || (n_graphs && !graphs)) throw DeviceError("null pointer");
+    *out = nullptr;
+    if (k % 2 == 0 || k < 11 || k > 31) throw DeviceError("--kmer must be an odd number between 11 and 31 (inclusive) for read-based depths");
+    std::vector<DepthGraphView> views(n_graphs);
+    std::vector<DepthGraphPlan> plans(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; g++) {
+        const ac_depth_graph& a = graphs[g];
+        if ((a.n_unitigs && (!a.seq_bytes || !a.seq_begin || !a.seq_len)) || (a.n_links && !a.links)) throw DeviceError("null pointer in graph " + std::to_string(g + 1));
+        static_assert(sizeof(ac_link) == 2 * sizeof(int32_t), "layout");
+        views[g] = DepthGraphView{a.seq_bytes, a.seq_begin, a.seq_len, a.n_unitigs, (const int32_t*)a.links, a.n_links};
+        depth_plan_graph(k, views[g], g, &plans[g]);
+    }
+    auto h = std::make_unique<ac_depth>();
+    h->device = device;
+    DeviceCall call(device);
+    h->e = std::make_unique<DepthEngine>(k, views, std::move(plans));      // (a failure on the way frees what the engine already held)
+    *out = h.release();
+}
+int ac_depth_begin(uint32_t k, const ac_depth_graph* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    return guarded([&] { depth_begin(k, graphs, n_graphs, device, out); });
+}
+int ac_depth_begin_handles(uint32_t k, const ac_graph* const* graphs, uint32_t n_graphs, int device, ac_depth** out) {
+    return guarded([&] {
+        if (n_graphs && !graphs) throw DeviceError("null pointer");
+        std::vector<ac_depth_graph> a(n_graphs);
+        for (uint32_t g = 0; g < n_graphs; g++) {
+            if (!graphs[g]) throw DeviceError("null pointer");
+            memset(&a[g], 0, sizeof a[g]);
+            if (ac_unitigs_bulk(graphs[g], &a[g].seq_bytes, &a[g].seq_begin, &a[g].seq_len, nullptr) || ac_links(graphs[g], &a[g].links, &a[g].n_links))
+                throw DeviceError(last_error());
+            a[g].n_unitigs = graphs[g]->g.n_unitigs;
+        }
+        depth_begin(k, a.data(), n_graphs, device, out);
+    });
+}
+static void depth_check_offsets(const uint8_t* bases, const uint64_t* read_off, uint64_t n_reads) {
+    if (n_reads && !read_off) throw DeviceError("null pointer");
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (read_off[r + 1] < read_off[r]) throw DeviceError("read_off must ascend (read " + std::to_string(r + 1) + " ends before it starts)");
+    if (n_reads && read_off[n_reads] > read_off[0] && !bases) throw DeviceError("null pointer");
+}
+int ac_depth_add_reads(ac_depth* d, const uint8_t* bases, const uint64_t* read_off, uint64_t n_reads) {
+    return guarded([&] {
+        if (!d) throw DeviceError("null pointer");
+        depth_check_offsets(bases, read_off, n_reads);
+        DeviceCall call(d->device);
+        d->e->add_reads(bases, read_off, n_reads);
+    });
+}
+int ac_depth_add_fastq(ac_depth* d, const char* path) {
+    return guarded([&] {
+        if (!d || !path) throw DeviceError("null pointer");
+        depth_read_fastq(path, (size_t)64 << 20, [&](const std::vector<uint8_t>& bases, const std::vector<uint64_t>& off) {
+            DeviceCall call(d->device);
+            d->e->add_reads(bases.data(), off.data(), off.size() - 1);
+        });
+    });
+}
+int ac_depth_totals_get(const ac_depth* d, ac_depth_totals* out) {
+    return guarded([&] {
+        if (!d || !out) throw DeviceError("null pointer");
+        if (out->size < sizeof(uint64_t)) throw DeviceError("ac_depth_totals.size must hold the caller's sizeof(ac_depth_totals)");
+        DeviceCall call(d->device);
+        const DepthTotals t = d->e->totals();
+        ac_depth_totals full;
+        memset(&full, 0, sizeof full);
+        full.size = sizeof full;
+        full.reads = t.reads; full.rejected_reads = t.rejected_reads; full.read_bases = t.read_bases; full.span_bases = t.span_bases;
+        full.span_kmers = t.span_kmers; full.hits = t.hits; full.distinct_kmers = t.distinct_kmers; full.repeat_kmers = t.repeat_kmers;
+        full.table_slots = t.table_slots; full.batches = t.batches; full.launches = t.launches; full.seconds_device = t.seconds_device;
+        memcpy(out, &full, std::min<size_t>((size_t)out->size, sizeof full));
+    });
+}
+int ac_depth_kmer_counts(ac_depth* d, const uint64_t* kmers, uint64_t n, uint8_t* present, uint32_t* assembly_occurrences, uint32_t* read_count) {
+    return guarded([&] {
+        if (!d || (n && !kmers)) throw DeviceError("null pointer");
+        DeviceCall call(d->device);
+        d->e->kmer_counts(kmers, n, present, assembly_occurrences, read_count);
+    });
+}
+int ac_depth_finish(ac_depth* d, uint32_t graph_index, double* depth, uint8_t* has_depth) {
+    return guarded([&] {
+        if (!d) throw DeviceError("null pointer");
+        if (graph_index >= d->e->n_graphs()) throw DeviceError("graph index out of range");
+        if (d->e->n_unitigs(graph_index) && (!depth || !has_depth)) throw DeviceError("null pointer");
+        DeviceCall call(d->device);
+        d->e->finish(graph_index, depth, has_depth);
+    });
+}
+void ac_depth_free(ac_depth* d) {
+    if (!d) return;
+    std::lock_guard<std::mutex> lock(g_build_mutex);
+    delete d;
+}
+
+// UnitigGraph::from_gfa_lines (unitig_graph.rs:55-174) for the GFAs `compress` writes: what `cluster` and `decompress` start from.
+int ac_graph_from_gfa(const char* gfa_text, uint64_t len, ac_graph** out) {
+    return guarded([&] {
+        if (!gfa_text) throw DeviceError("no GFA text");
+        auto h = std::make_unique<ac_graph>();
+        std::vector<SeqMeta> meta;
+        load_gfa(gfa_text, (size_t)len, &h->g, &meta);
+        for (auto& m : meta) { h->seq_ids.push_back(m.id); h->seq_lens.push_back(m.length); h->filenames.push_back(m.filename); h->headers.push_back(m.contig_header); }
+        *out = h.release();
+    });
+}
+// reconstruct_original_sequences (unitig_graph.rs:362-388) for one sequence; out holds its LN bytes.
+int ac_decompress_seq(const ac_graph* g, uint32_t seq_index, uint8_t* out) {
+    return guarded([&] {
+        if (seq_index >= g->seq_ids.size()) throw DeviceError("sequence index out of range");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        decompress_sequence(g->g, seq_index, (char*)out);
+    });
+}
+
+// ---- the round-trip verifier behind the ABI (kernels_verify.inc) ------------------------------------------------------------------
+static void fill_report(const VerifyReport& r, ac_verify_report* o) {
+    memset(o, 0, sizeof *o);
+    o->failed = r.failed;
+    o->first_bad_unitig = r.first_bad_unitig; o->first_bad_link = r.first_bad_link; o->first_bad_path_entry = r.first_bad_path_entry;
+    o->first_bad_sequence = r.first_bad_sequence; o->first_bad_base = r.first_bad_base;
+    o->unitigs = r.unitigs; o->links = r.links; o->path_entries = r.path_entries; o->bases_checked = r.bases_checked;
+    o->self_mirror_links = r.self_mirror_links; o->seconds = r.seconds;
+    o->checks = r.checks; o->first_bad_junction = r.first_bad_junction;
+}
+int ac_verify_graph_device(const ac_graph* g, const void* d_text, uint64_t n_text, const uint64_t* seq_off, const uint32_t* seq_len,
+                           uint32_t n_seqs, int device, ac_verify_report* report) {
+    return guarded([&] {
+        if (!g || !d_text || !seq_off || !seq_len || !report) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        if (n_seqs != g->seq_lens.size()) throw DeviceError("ac_verify_graph: the graph was built from " + std::to_string(g->seq_lens.size()) + " sequences, not " + std::to_string(n_seqs));
+        DeviceCall call(device);
+        std::vector<uint64_t> off(seq_off, seq_off + n_seqs);
+        std::vector<uint32_t> len(seq_len, seq_len + n_seqs);
+        VerifyReport r;
+        verify_graph_device(g->g, (const uint8_t*)d_text, n_text, off, len, &r);
+        fill_report(r, report);
+    });
+}
+int ac_verify_graph(const ac_graph* g, const ac_seq_view* seqs, uint32_t n_seqs, int device, ac_verify_report* report) {
+    return guarded([&] {
+        if (!g || !seqs || !report) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        if (n_seqs != g->seq_lens.size()) throw DeviceError("ac_verify_graph: the graph was built from " + std::to_string(g->seq_lens.size()) + " sequences, not " + std::to_string(n_seqs));
+        std::vector<SeqView> v(n_seqs);
+        for (uint32_t i = 0; i < n_seqs; i++) {
+            if (!seqs[i].fwd) throw DeviceError("null sequence");
+            v[i] = SeqView{seqs[i].fwd, seqs[i].length};
+        }
+        std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint16_t> d1, d2;
+        std::vector<uint8_t> text = layout_text(v, g->g.k, &off, &len, &d1, &d2);
+        DeviceCall call(device);
+        VerifyReport r;
+        // (the text goes up through an allocation of its own: the verifier resets the arena for its working set)
+#ifdef AC_EMU
+        verify_graph_device(g->g, text.data(), text.size(), off, len, &r);
+#else
+        void* d_text = nullptr;
+        AC_HIP_CHECK(hipMalloc(&d_text, text.size() + 64));
+        struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{d_text};
+        AC_HIP_CHECK(hipMemcpy(d_text, text.data(), text.size(), hipMemcpyHostToDevice));
+        verify_graph_device(g->g, (const uint8_t*)d_text, text.size(), off, len, &r);
+#endif
+        fill_report(r, report);
+    });
+}
+
+// reconstruct_original_sequences for every sequence of the graph at once, on the device (kernels_verify.inc): out = sum of the sequence
+// lengths bytes, sequence i at offset sum(length[0 .. i)).  What ac_decompress_seq does one sequence at a time on the host.
+int ac_decompress_device(const ac_graph* g, int device, uint8_t* out, uint64_t out_bytes) {
+    return guarded([&] {
+        if (!g || !out) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        uint64_t need = 0;
+        for (uint32_t l : g->seq_lens) need += l;
+        if (out_bytes < need) throw DeviceError("ac_decompress_device: the buffer holds " + std::to_string(out_bytes) + " bytes, the sequences need " + std::to_string(need));
+        DeviceCall call(device);
+        decompress_device(g->g, g->seq_lens, out);
+    });
+}
+// The hand-written scan / radix sort / comparator sort (device_prims.hpp) against the host's std:: algorithms — test hook.
+int ac_selftest_primitives(int device, uint64_t n, uint64_t seed, int end_bit, int key_kind) {
+    return guarded([&] {
+        if (end_bit < 1 || end_bit > 64) throw DeviceError("end_bit out of range");
+        DeviceCall call(device);
+        primitives_selftest(n, seed, end_bit, key_kind);
+    });
+}
+
+int ac_random_access_ceilings_at(int device, uint64_t table_slots, double* cas_gops, double* read_gops) {
+    return guarded([&] {
+        DeviceCall call(device);
+        random_access_ceilings(cas_gops, read_gops, table_slots);
+    });
+}
+int ac_random_access_ceilings(int device, double* cas_gops, double* read_gops) { return ac_random_access_ceilings_at(device, (uint64_t)1 << 24, cas_gops, read_gops); }
+
+}  // extern "C"

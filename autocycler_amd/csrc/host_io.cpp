@@ -207,7 +207,7 @@ LoadResult load_sequences(const std::string& assemblies_dir, uint32_t k, uint32_
         throw UserError(std::string("the mean number of contigs per input assembly (") + buf + ") exceeds the allowed threshold (" +
                         std::to_string(max_contigs) + "). Are your input assemblies fragmented or contaminated?");
     }
-    lr.load_seconds = now_s() - t0;      // (sequence_end_repair, compress.rs:202-270, is a device kernel: neighbours.inc — the callers in capi.cpp run it)
+    lr.load_seconds = now_s() - t0;      // (sequence_end_repair, compress.rs:202-270, is a device kernel: neighbours.inc — the callers in capi_command.cpp run it)
     lr.repair_seconds = 0;
     return lr;
 }

@@ -1,4 +1,4 @@
-// Host-only microbenchmark of the GFA emission of the whole command (gfa_chunks + the parallel pwrite of capi.cpp's write_pieces) on a
+// Host-only microbenchmark of the GFA emission of the whole command (gfa_chunks + the parallel pwrite of capi_command.cpp's write_pieces) on a
 // synthetic graph of config C's shape: 158 639 unitigs (5.7 M bases), 212 353 links, 171 paths with 10.6 M entries -> a 95 MB file.
 //   g++ -O2 -std=c++17 -pthread -I autocycler_amd/csrc tools/microbench/gfa_write_bench.cpp autocycler_amd/csrc/gfa_writer.cpp -o /tmp/gfa_write_bench
 //   /tmp/gfa_write_bench [threads] [dir]
