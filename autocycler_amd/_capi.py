@@ -100,7 +100,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -185,6 +185,12 @@ def load_library(path=None):
     lib.ac_depth_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.ac_depth_free.argtypes = [C.c_void_p]
     lib.ac_depth_free.restype = None
+    lib.ac_selftest_scan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.ac_selftest_radix.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_segments.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.ac_selftest_sort_cmp.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_scan_pool.argtypes = [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.ac_selftest_wave.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[key] = lib
     return lib
 
@@ -516,6 +522,89 @@ class ReadDepth:
         depth = (C.c_double * max(n, 1))(); has = (C.c_uint8 * max(n, 1))()
         _check(self._lib, self._lib.ac_depth_finish(self._h, C.c_uint32(graph_index), depth, has))
         return [depth[i] if has[i] else None for i in range(n)]
+
+
+# ---- test hooks: one device primitive on numpy arrays (ac_selftest_*; tests/prim_cases.py holds the references) ----
+SCAN_KINDS = {"incl_add_u32": 0, "excl_add_u32": 1, "incl_max_u32": 2, "excl_add_u64": 3}
+
+
+def _np_in(a, dtype):
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def selftest_scan(kind, values, in_place=False, misalign_in=0, misalign_out=0, device=0, lib_path=None):
+    """ac_selftest_scan: kind is a key of SCAN_KINDS -> the scanned array."""
+    import numpy as np
+    lib = load_library(lib_path)
+    a = _np_in(values, np.uint64 if kind == "excl_add_u64" else np.uint32)
+    out = np.empty_like(a)
+    _check(lib, lib.ac_selftest_scan(device, SCAN_KINDS[kind], a.ctypes.data, a.size, int(in_place), misalign_in, misalign_out, out.ctypes.data))
+    return out
+
+
+def selftest_radix(keys, vals, begin_bit, end_bit, prep_n=0, prep_bits=0, prep_reuse=False, device=0, lib_path=None):
+    """ac_selftest_radix: vals of dtype int32 take the i32 form, anything else the u32 form -> (keys, vals) sorted on [begin_bit, end_bit)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    k = _np_in(keys, np.uint64)
+    signed = np.asarray(vals).dtype == np.int32
+    v = _np_in(vals, np.int32 if signed else np.uint32)
+    ko, vo = np.empty_like(k), np.empty_like(v)
+    _check(lib, lib.ac_selftest_radix(device, k.ctypes.data, v.ctypes.data, k.size, begin_bit, end_bit, int(signed), prep_n, prep_bits, int(prep_reuse),
+                                      ko.ctypes.data, vo.ctypes.data))
+    return ko, vo
+
+
+def selftest_segments(op, seg, vals, n_segments, deferred_err=False, device=0, lib_path=None):
+    """ac_selftest_segments: op "min" (reduce_by_segment) or "argmin" (segment_argmin) -> (out[n_segments], error word)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    s, v = _np_in(seg, np.uint32), _np_in(vals, np.uint64)
+    out = np.empty(n_segments, dtype=np.uint64 if op == "min" else np.uint32)
+    err = C.c_uint32()
+    _check(lib, lib.ac_selftest_segments(device, {"min": 0, "argmin": 1}[op], s.ctypes.data, v.ctypes.data, s.size, n_segments, int(deferred_err), out.ctypes.data,
+                                         C.byref(err)))
+    return out, err.value
+
+
+def selftest_sort_pairs_cmp(key_a, key_b, vals, device=0, lib_path=None):
+    """ac_selftest_sort_cmp, form 0: sort_by_key_cmp of the keys (key_a[i], key_b[i]) with the payload vals[i] -> (key_a, key_b, vals)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    a, b, v = _np_in(key_a, np.uint64), _np_in(key_b, np.uint32), _np_in(vals, np.uint32)
+    ao, bo, vo = np.empty_like(a), np.empty_like(b), np.empty_like(v)
+    _check(lib, lib.ac_selftest_sort_cmp(device, 0, a.ctypes.data, b.ctypes.data, v.ctypes.data, a.size, ao.ctypes.data, bo.ctypes.data, vo.ctypes.data))
+    return ao, bo, vo
+
+
+def selftest_sort_indices_cmp(values, indices, device=0, lib_path=None):
+    """ac_selftest_sort_cmp, form 1: sort_keys_cmp of `indices` by values[index] -> the sorted indices."""
+    import numpy as np
+    lib = load_library(lib_path)
+    a, v = _np_in(values, np.uint64), _np_in(indices, np.uint32)
+    vo = np.empty_like(v)
+    _check(lib, lib.ac_selftest_sort_cmp(device, 1, a.ctypes.data, None, v.ctypes.data, v.size, None, None, vo.ctypes.data))
+    return vo
+
+
+def selftest_scan_pool(op="read", value=0, device=0, lib_path=None):
+    """ac_selftest_scan_pool: op "read", "advance" (the epoch forward to value) or "invalidate" -> dict(cap, epoch, tickets) afterwards."""
+    lib = load_library(lib_path)
+    out = (C.c_uint64 * 3)()
+    _check(lib, lib.ac_selftest_scan_pool(device, {"read": 0, "advance": 1, "invalidate": 2}[op], value, out))
+    return dict(cap=out[0], epoch=out[1], tickets=out[2])
+
+
+def selftest_wave(program, in_u64, aux_i32, live_mask, out_init, device=0, lib_path=None):
+    """ac_selftest_wave: program number (WaveProgram, csrc/selftest_prims.inc); in_u64, aux_i32, out_init: 256 items; live_mask: 4 words."""
+    import numpy as np
+    lib = load_library(lib_path)
+    i, a, m = _np_in(in_u64, np.uint64), _np_in(aux_i32, np.int32), _np_in(live_mask, np.uint64)
+    out = np.array(out_init, dtype=np.uint64)
+    assert i.size == 256 and a.size == 256 and m.size == 4 and out.size == 256
+    _check(lib, lib.ac_selftest_wave(device, program, i.ctypes.data, a.ctypes.data, m.ctypes.data, out.ctypes.data))
+    return out
 
 
 class VerifyReport(C.Structure):

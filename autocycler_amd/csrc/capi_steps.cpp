@@ -308,6 +308,27 @@ int ac_selftest_primitives(int device, uint64_t n, uint64_t seed, int end_bit, i
         primitives_selftest(n, seed, end_bit, key_kind);
     });
 }
+// One primitive on the caller's arrays, its output handed back — test hooks (selftest_prims.inc).
+int ac_selftest_scan(int device, int kind, const void* in, uint64_t n, int in_place, int misalign_in, int misalign_out, void* out) {
+    return guarded([&] { DeviceCall call(device); selftest_scan(kind, in, n, in_place != 0, misalign_in, misalign_out, out); });
+}
+int ac_selftest_radix(int device, const uint64_t* keys, const void* vals, uint64_t n, int begin_bit, int end_bit, int val_kind, uint64_t prep_n, int prep_bits,
+                      int prep_reuse, uint64_t* keys_out, void* vals_out) {
+    return guarded([&] { DeviceCall call(device); selftest_radix(keys, vals, n, begin_bit, end_bit, val_kind, prep_n, prep_bits, prep_reuse != 0, keys_out, vals_out); });
+}
+int ac_selftest_segments(int device, int op, const uint32_t* seg, const uint64_t* vals, uint64_t n, uint64_t n_segments, int deferred_err, void* out, uint32_t* err_out) {
+    return guarded([&] { DeviceCall call(device); selftest_segments(op, seg, vals, n, n_segments, deferred_err != 0, out, err_out); });
+}
+int ac_selftest_sort_cmp(int device, int form, const uint64_t* key_a, const uint32_t* key_b, const uint32_t* vals, uint64_t n, uint64_t* key_a_out, uint32_t* key_b_out,
+                         uint32_t* vals_out) {
+    return guarded([&] { DeviceCall call(device); selftest_sort_cmp(form, key_a, key_b, vals, n, key_a_out, key_b_out, vals_out); });
+}
+int ac_selftest_scan_pool(int device, int op, uint64_t value, uint64_t* out) {
+    return guarded([&] { DeviceCall call(device); selftest_scan_pool(op, value, out); });
+}
+int ac_selftest_wave(int device, int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64) {
+    return guarded([&] { DeviceCall call(device); selftest_wave(program, in_u64, aux_i32, live_mask, out_u64); });
+}
 
 int ac_random_access_ceilings_at(int device, uint64_t table_slots, double* cas_gops, double* read_gops) {
     return guarded([&] {

@@ -19,7 +19,17 @@ namespace ac {
 
 // ---- one state word per tile ---------------------------------------------------------------------------------------------------
 #ifdef AC_EMU
-inline u64 state_load(const u64* p) { return *p; }
+// (the emulation runs the tiles one after the other in ticket order: a look-back that reads the same word with the same content a million
+// times waits for a tile that will never publish — a stale ticket counter, a pool that was not cleared — and is reported, not spun on)
+inline u64 state_load(const u64* p) {
+    struct Seen { const u64* p; u64 v; u32 n; };
+    static thread_local Seen seen[1024];
+    Seen& e = seen[wv::tid() & 1023u];
+    const u64 v = *p;
+    if (e.p == p && e.v == v) { if (++e.n > (1u << 20)) { e.n = 0; throw DeviceError("lockstep emulation: a look-back waits for a tile state that is never published"); } }
+    else { e.p = p; e.v = v; e.n = 0; }
+    return v;
+}
 inline void state_store(u64* p, u64 v) { *p = v; }
 #else
 __device__ inline u64 state_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -253,4 +253,6 @@ void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind) {
     stream_sync();
 }
 
+#include "selftest_prims.inc"      // the data-in / data-out hooks: one primitive on the caller's arrays (ac_selftest_scan, ...)
+
 }  // namespace ac

@@ -187,6 +187,14 @@ void overlap_alignment_batch(const std::vector<AlignJob>& jobs, const uint32_t* 
 uint32_t trim_max_unitigs();      // largest min(max_unitigs, path length) the alignment kernels take
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
+// One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.
+void selftest_scan(int kind, const void* in, uint64_t n, bool in_place, int misalign_in, int misalign_out, void* out);
+void selftest_radix(const uint64_t* keys, const void* vals, uint64_t n, int begin_bit, int end_bit, int val_kind, uint64_t prep_n, int prep_bits, bool prep_reuse,
+                    uint64_t* keys_out, void* vals_out);
+void selftest_segments(int op, const uint32_t* seg, const uint64_t* vals, uint64_t n, uint64_t n_segments, bool deferred_err, void* out, uint32_t* err_out);
+void selftest_sort_cmp(int form, const uint64_t* a, const uint32_t* b, const uint32_t* vals, uint64_t n, uint64_t* a_out, uint32_t* b_out, uint32_t* vals_out);
+void selftest_scan_pool(int op, uint64_t value, uint64_t* out);
+void selftest_wave(int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64);
 
 // Measured ceilings of the device for random atomicCAS / random 8-byte reads on a 134 MB table, in 10^9 operations per second.
 void random_access_ceilings(double* cas_gops, double* read_gops, uint64_t table_slots = (uint64_t)1 << 24);

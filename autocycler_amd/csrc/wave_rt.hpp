@@ -35,7 +35,7 @@ __device__ __forceinline__ int shfl_down(int v, int d) { return __shfl_down(v, d
 template <int G> __device__ __forceinline__ unsigned long long grp_ballot(bool p, int gshift) {
     return (__ballot(p) >> gshift) & (G == 64 ? ~0ULL : ((1ULL << G) - 1));
 }
-template <int G> __device__ __forceinline__ int grp_shfl(int v, int src_in_group, int gshift) { return __shfl(v, gshift + src_in_group); }
+template <int G> __device__ __forceinline__ int grp_shfl(int v, int src_in_group, int gshift) { return __shfl(v, gshift + (src_in_group & (G - 1))); }      // (the source modulo G: never a lane of another group)
 __device__ __forceinline__ void block_sync() { __syncthreads(); }
 } }
 #else

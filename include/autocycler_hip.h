@@ -165,6 +165,38 @@ int ac_decompress_device(const ac_graph*, int device, uint8_t* out, uint64_t out
  * n pseudo-random items; key_kind 0 uniform, 1 few distinct values, 2 sorted, 3 reverse sorted, 4 one hot digit.  0 = equal. */
 int ac_selftest_primitives(int device, uint64_t n, uint64_t seed, int end_bit, int key_kind);
 
+/* Test hooks, data in / data out: ONE primitive of csrc/device_prims.hpp or csrc/wave_rt.hpp on the caller's host arrays, its output handed
+ * back — the reference is the caller's (tests/prim_cases.py: numpy and Python integers).  Additive to ABI 7.  All arrays are host memory.
+ *   ac_selftest_scan       kind 0 u32 inclusive add, 1 u32 exclusive add, 2 u32 inclusive max, 3 u64 exclusive add; in / out hold n items of
+ *                          that width.  in_place: the scan writes over its input.  misalign_in / misalign_out: the device pointers start that
+ *                          many ELEMENTS behind a 16-byte boundary (below 4 for u32, below 2 for u64).  The grand total of an add scan must
+ *                          stay below 2^46 for u64 items (the documented limit; a u32 scan is exact modulo 2^32 whatever its total); totals at
+ *                          or above it and more than 2^32 items are outside what the hooks test.
+ *   ac_selftest_radix      the stable sort of (u64 key, 32-bit value) pairs on key bits [begin_bit, end_bit).  val_kind 0: u32 values, 1: i32
+ *                          values (no prepared scratch there).  prep_n != 0: a RadixScratch prepared for (prep_n items, prep_bits key bits) is
+ *                          handed to the sort, which falls back to its own if that one is too small; prep_reuse != 0: the prepared scratch has
+ *                          already been used up by another sort when the sort under test gets it.
+ *   ac_selftest_segments   op 0: reduce_by_segment with the u64 minimum, out = uint64_t[n_segments]; op 1: segment_argmin with "the index of
+ *                          the smaller vals[], the lower index on ties", out = uint32_t[n_segments].  seg: non-decreasing ids that step by one.
+ *                          Entries of out that no segment wrote come back with all bits set.  deferred_err != 0: the error-word form, the word
+ *                          in *err_out (bit 128: n_segments is not the number of segments); otherwise such a mismatch is an error return.
+ *   ac_selftest_sort_cmp   form 0: sort_by_key_cmp of the keys (key_a[i], key_b[i]), compared field by field, with the payload vals[i]; form 1:
+ *                          sort_keys_cmp of the indices vals[i] (each below n) by key_a[index] (key_b and the key outputs unused).  Both stable.
+ *   ac_selftest_scan_pool  the calling thread's scan state pool.  op 0: read; 1: its epoch forward to `value` (never back, below 2^16); 2:
+ *                          invalidate().  out[3] = {capacity in words, epoch, tickets handed out} afterwards.
+ *   ac_selftest_wave       one workgroup of 256 threads; thread t returns before any cross-lane operation if bit t of live_mask[4] is clear,
+ *                          the others run `program` — one primitive of wave_rt.hpp each, numbered as WaveProgram in csrc/selftest_prims.inc —
+ *                          on in_u64[t] / aux_i32[t] (aux_i32[0] where the primitive takes one distance) and write out_u64[t]; a returned
+ *                          thread's out_u64[t] stays as the caller left it. */
+int ac_selftest_scan(int device, int kind, const void* in, uint64_t n, int in_place, int misalign_in, int misalign_out, void* out);
+int ac_selftest_radix(int device, const uint64_t* keys, const void* vals, uint64_t n, int begin_bit, int end_bit, int val_kind, uint64_t prep_n, int prep_bits,
+                      int prep_reuse, uint64_t* keys_out, void* vals_out);
+int ac_selftest_segments(int device, int op, const uint32_t* seg, const uint64_t* vals, uint64_t n, uint64_t n_segments, int deferred_err, void* out, uint32_t* err_out);
+int ac_selftest_sort_cmp(int device, int form, const uint64_t* key_a, const uint32_t* key_b, const uint32_t* vals, uint64_t n, uint64_t* key_a_out, uint32_t* key_b_out,
+                         uint32_t* vals_out);
+int ac_selftest_scan_pool(int device, int op, uint64_t value, uint64_t* out);
+int ac_selftest_wave(int device, int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64);
+
 /* The 2-bit packing the host entry applies before the upload (sequence.rs:39-48 validates the same alphabet): n_text bytes ->
  * (n_text + 31) / 32 words of 2-bit codes (A, C, G, T = 0..3, first base most significant) and as many 32-bit mask words
  * (bit i = byte i is not a base).  force_scalar != 0 selects the portable loop instead of the AVX2 / BMI2 one (both are
