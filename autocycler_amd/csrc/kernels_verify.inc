@@ -307,10 +307,15 @@ void verify_graph_device(const FinalGraph& g, const uint8_t* d_text, uint64_t n_
     u64 seq_total = 0, total_len = 0;
     for (u64 i = 0; i < U; i++) { seq_total = std::max<u64>(seq_total, g.seq_begin[i] + g.seq_len[i]); total_len += g.seq_len[i]; }
     if (seq_total > g.seq_block.bytes && g.seq_block.bytes) seq_total = g.seq_block.bytes;      // (a range beyond the block is reported per unitig)
+    // offsets that do not ascend from 0 to the number of entries: every kernel below indexes the entries through them, so the run ends here
+    // with the first sequence whose range is no range (the last one when the offsets end beside the entries)
     u32 host_flags = 0;
-    if (g.path_off[0] != 0 || g.path_off[n_seqs] != n_ent) host_flags |= VF_PATH_LEN;
-    for (u32 s = 0; s < n_seqs; s++) if (g.path_off[s + 1] < g.path_off[s]) host_flags |= VF_PATH_LEN;
-    if (host_flags & VF_PATH_LEN) { rep->failed = host_flags; rep->first_bad_sequence = 0; rep->seconds = now_s() - t0; return; }
+    u64 bad_seq = ~0ULL;
+    if (g.path_off[n_seqs] != n_ent) bad_seq = n_seqs - 1;
+    for (u32 s = n_seqs; s-- > 0;) if (g.path_off[s + 1] < g.path_off[s]) bad_seq = s;
+    if (g.path_off[0] != 0) bad_seq = 0;
+    if (bad_seq != ~0ULL) host_flags |= VF_PATH_LEN;
+    if (host_flags & VF_PATH_LEN) { rep->failed = host_flags; rep->first_bad_sequence = bad_seq; rep->seconds = now_s() - t0; return; }
 
     Arena::device().reset();
     DBuf<u64> err(8);

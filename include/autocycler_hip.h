@@ -128,6 +128,9 @@ size_t ac_multi_info_get_sized(const ac_graph*, ac_multi_info* out, size_t out_s
  * `failed` bits: 1 unitig length / range, 2 renumber order, 4 link endpoint out of range, 8 duplicate link, 16 link without mirror,
  * 32 path entry out of range, 64 path step that is no link, 128 path length != sequence length, 256 a path does not spell its sequence,
  * 512 depth != occurrences, 1024 statistics.  first_bad_*: the smallest offending index of each kind (all ones: none).
+ * Path offsets that do not ascend from 0 to the number of path entries end the run at once: failed = 128, first_bad_sequence = the first
+ * sequence whose offsets are no range (the last sequence when the offsets end beside the entries), checks = 0 and nothing else filled in —
+ * every other check reaches the entries through them.
  *
  * ABI 6 adds the three ORDER-SENSITIVE guarantees of the reference, so that a graph no CPU oracle can hold is checked as "the reference's
  * graph" and not only as "lossless and consistent" (the struct grew at its end: `checks`, `first_bad_junction`):

@@ -168,6 +168,18 @@ def test_verify_graph_names_order_sensitive_damage(emu):
     verify_cases.names_order_sensitive_damage(emu)
 
 
+@pytest.mark.parametrize("family", ["bases", "lengths", "depth", "links", "link_kinds", "link_order", "paths", "path_off", "inputs", "gfa", "junctions", "large"])
+def test_verify_graph_mutation_sweep(emu, family):
+    # every mutant's WHOLE report == tests/verify_model.py (the verifier restated in plain Python); see verify_cases.sweep_coverage
+    import verify_cases
+    assert len(verify_cases.sweep(emu, family)) >= 12
+
+
+def test_verify_graph_mutation_sweep_coverage(emu):
+    import verify_cases
+    verify_cases.sweep_coverage(emu)
+
+
 @pytest.mark.parametrize("kind", [0, 1, 2, 3, 4])
 def test_hand_written_primitives_equal_std(emu, kind):
     # csrc/device_prims.hpp (scan with decoupled look-back, onesweep radix sort, merge sort by ranks) under the lockstep emulation: tile

@@ -129,6 +129,26 @@ def test_verify_graph_names_order_sensitive_damage(lib):
     verify_cases.names_order_sensitive_damage(None)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["bases", "lengths", "depth", "links", "link_kinds", "link_order", "paths", "path_off", "inputs", "gfa", "junctions", "large"])
+def test_verify_graph_mutation_sweep(lib, family):
+    # every mutant's WHOLE report == tests/verify_model.py (the verifier restated in plain Python); see verify_cases.sweep_coverage
+    import verify_cases
+    assert len(verify_cases.sweep(None, family)) >= 12
+
+
+@pytest.mark.gpu
+def test_verify_graph_mutation_sweep_coverage(lib):
+    import verify_cases
+    verify_cases.sweep_coverage(None)
+
+
+@pytest.mark.gpu
+def test_verify_graph_device_text_names_the_same_damage(lib):
+    import verify_cases
+    verify_cases.device_text_equals_host(None)
+
+
 @pytest.mark.parametrize("kind", [0, 1, 2, 3, 4])
 def test_hand_written_primitives_equal_std(lib, kind):
     # csrc/device_prims.hpp on the device: thousands of tiles in flight (the look-back chains), every key kind, odd end bits
