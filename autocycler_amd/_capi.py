@@ -82,6 +82,20 @@ class AlignmentPiece(C.Structure):
 ALIGN_GAP, ALIGN_NONE = 0, 0xFFFFFFFF
 
 
+class Bridge(C.Structure):      # ac_bridge
+    _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("depth", C.c_uint32), ("n_distinct", C.c_uint32), ("best_off", C.c_uint64),
+                ("best_total", C.c_uint64), ("first_distinct", C.c_uint64), ("best_len", C.c_uint32), ("status", C.c_uint32),
+                ("conflicting", C.c_uint32), ("culled", C.c_uint32), ("cull_rank", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ResolveSummary(C.Structure):
+    _fields_ = [("size", C.c_uint64), ("jobs", C.c_uint64), ("jobs_not_launched", C.c_uint64), ("cells", C.c_uint64), ("largest_job_cells", C.c_uint64),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("size", "reserved")}
+
+
 class DepthGraph(C.Structure):      # ac_depth_graph
     _fields_ = [("seq_bytes", C.c_void_p), ("seq_begin", C.c_void_p), ("seq_len", C.c_void_p), ("n_unitigs", C.c_uint32),
                 ("links", C.c_void_p), ("n_links", C.c_uint64)]
@@ -100,7 +114,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -176,6 +190,20 @@ def load_library(path=None):
                                         C.POINTER(TrimResult), C.POINTER(TrimSummary)]
     lib.ac_overlap_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_int,
                                          C.POINTER(AlignmentPiece), C.POINTER(C.c_uint32)]
+    lib.ac_resolve_max_path.restype = C.c_uint32
+    lib.ac_resolve_max_path.argtypes = []
+    lib.ac_resolve_bridges.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_resolve_bridge_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_path_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    lib.ac_resolve_anchors.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+    lib.ac_resolve_bridge_records.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Bridge)), C.POINTER(C.c_uint32)]
+    lib.ac_resolve_best_paths.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_uint64)]
+    lib.ac_resolve_distinct_paths.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32)),
+                                              C.POINTER(C.c_uint64)]
+    lib.ac_resolve_summary_get_sized.restype = C.c_size_t
+    lib.ac_resolve_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ResolveSummary), C.c_size_t]
+    lib.ac_resolve_free.argtypes = [C.c_void_p]
+    lib.ac_resolve_free.restype = None
     lib.ac_depth_begin.argtypes = [C.c_uint32, C.POINTER(DepthGraph), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_begin_handles.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_add_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
@@ -323,6 +351,13 @@ class Graph:
         _check(self._lib, self._lib.ac_trim_paths(self._h, min_identity, max_unitigs, device, out, C.byref(sm)))
         return [out[i].as_dict() for i in range(n)], sm.as_dict()
 
+    def resolve_bridges(self, device=0):
+        """The compute of `autocycler resolve` up to the graph edits (ac_resolve_bridges) on this graph's paths, unitig lengths and
+        headers.  Returns (anchors, bridges, summary) as resolve_bridge_paths does."""
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_resolve_bridges(self._h, device, C.byref(h)))
+        return _resolve_result(self._lib, h)
+
     def verify(self, seqs, device=0):
         """ac_verify_graph: the round-trip verifier on the device (decompress identity, check_links, depth, renumber order, statistics).
         seqs: [(padded forward bytes, unpadded length, id)] as for compress_build.  Returns the report as a dict; report["failed"] == 0
@@ -424,6 +459,72 @@ def trim_path_slices(paths, weights, min_identity=0.75, max_unitigs=5000, device
     sm = TrimSummary(size=C.sizeof(TrimSummary))
     _check(lib, lib.ac_trim_path_slices(ent, offs, len(paths), w, nw, min_identity, max_unitigs, device, out, C.byref(sm)))
     return [out[i].as_dict() for i in range(len(paths))], sm.as_dict()
+
+
+def _flat_paths(paths):
+    flat = [x for p in paths for x in p]
+    off = [0]
+    for p in paths:
+        off.append(off[-1] + len(p))
+    return (C.c_int32 * max(len(flat), 1))(*flat), (C.c_uint64 * len(off))(*off)
+
+
+def max_resolve_path(lib_path=None):
+    """ac_resolve_max_path: the longest path a distance job takes."""
+    return load_library(lib_path).ac_resolve_max_path()
+
+
+def path_distances(paths, pairs, weights, device=0, lib_path=None):
+    """global_alignment_distance (resolve.rs:387-418) on the device (ac_path_distances) for pairs (a, b) of indices into `paths` (lists of
+    signed unitig numbers).  Returns (distances, statuses): status 2 = the two paths' weights add up to 2^32 or more, not computed."""
+    lib = load_library(lib_path)
+    ent, offs = _flat_paths(paths)
+    n = len(pairs)
+    pa = (C.c_uint32 * max(n, 1))(*[a for a, _ in pairs]); pb = (C.c_uint32 * max(n, 1))(*[b for _, b in pairs])
+    w, nw = _weights_array(weights)
+    dist = (C.c_uint32 * max(n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    _check(lib, lib.ac_path_distances(ent, offs, len(paths), pa, pb, n, w, nw, device, dist, status))
+    return list(dist)[:n], list(status)[:n]
+
+
+def _resolve_result(lib, h):
+    try:
+        ap, an = C.POINTER(C.c_uint32)(), C.c_uint32()
+        _check(lib, lib.ac_resolve_anchors(h, C.byref(ap), C.byref(an)))
+        anchors = ap[:an.value]
+        bp, bn = C.POINTER(Bridge)(), C.c_uint32()
+        _check(lib, lib.ac_resolve_bridge_records(h, C.byref(bp), C.byref(bn)))
+        best, nbest = C.POINTER(C.c_int32)(), C.c_uint64()
+        _check(lib, lib.ac_resolve_best_paths(h, C.byref(best), C.byref(nbest)))
+        de, do, dm, dn = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.c_uint64()
+        _check(lib, lib.ac_resolve_distinct_paths(h, C.byref(de), C.byref(do), C.byref(dm), C.byref(dn)))
+        bridges = []
+        for i in range(bn.value):
+            b = bp[i]
+            assert b.best_off + b.best_len <= nbest.value and b.first_distinct + b.n_distinct <= dn.value
+            distinct = [(de[do[q]:do[q + 1]], dm[q]) for q in range(b.first_distinct, b.first_distinct + b.n_distinct)]
+            bridges.append(dict(start=b.start, end=b.end, depth=b.depth, status=b.status,
+                                best_path=best[b.best_off:b.best_off + b.best_len] if b.status == 0 else None,
+                                best_total=b.best_total if b.status == 0 else None, distinct_paths=distinct,
+                                conflicting=b.conflicting, culled=b.culled, cull_rank=b.cull_rank))
+        sm = ResolveSummary()
+        assert lib.ac_resolve_summary_get_sized(h, C.byref(sm), C.sizeof(ResolveSummary)) == C.sizeof(ResolveSummary)
+        return anchors, bridges, sm.as_dict()
+    finally:
+        lib.ac_resolve_free(h)
+
+
+def resolve_bridge_paths(paths, weights, consensus_weights=None, device=0, lib_path=None):
+    """ac_resolve_bridge_paths: anchors, bridges (Bridge::cmp order) and a summary for the sequences' paths (lists of signed unitig
+    numbers).  A bridge is a dict: start, end, depth, status (2: the reference's u32 arithmetic would overflow; best_path is None),
+    best_path, best_total, distinct_paths [(path, multiplicity)], conflicting, culled, cull_rank (1-based; 0 = kept)."""
+    lib = load_library(lib_path)
+    ent, offs = _flat_paths(paths)
+    w, nw = _weights_array(weights)
+    cw = (C.c_uint32 * max(len(paths), 1))(*consensus_weights) if consensus_weights is not None else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_resolve_bridge_paths(ent, offs, len(paths), cw, w, nw, device, C.byref(h)))
+    return _resolve_result(lib, h)
 
 
 class ReadDepth:

@@ -1,8 +1,9 @@
-// C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, read depths, the
+// C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, resolve, read depths, the
 // verifier, decompress, the GFA reload, and the self-tests of the device primitives.
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "capi_common.hpp"
 #include "gfa_writer.hpp"
@@ -112,6 +113,128 @@ int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const u
     });
 }
 uint32_t ac_trim_max_unitigs(void) { return trim_max_unitigs(); }
+
+// ---- `autocycler resolve`: anchors, bridges and their best paths.  The path distances on the device (kernels_resolve.inc), everything around
+// them on the host (resolve_host.cpp).  Applying the bridges to the graph stays with the caller ----
+struct ac_resolve {
+    ResolveResult r;
+    std::vector<ac_bridge> records;
+    ac_resolve_summary summary;
+};
+static void check_path_table(const int32_t* entries, const uint64_t* off, uint32_t n_paths, uint32_t n_weights, const char* what) {
+    if (n_paths && (!off || (off[n_paths] > off[0] && !entries))) throw DeviceError("null pointer");
+    for (uint32_t p = 0; p < n_paths; p++) {
+        if (off[p + 1] < off[p]) throw DeviceError("path offsets must ascend");
+        validate_resolve_path(entries + off[p], off[p + 1] - off[p], n_weights, (std::string(what) + " " + std::to_string(p + 1)).c_str());
+    }
+}
+int ac_path_distances(const int32_t* entries, const uint64_t* path_off, uint32_t n_paths, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                      const uint32_t* weights, uint32_t n_weights, int device, uint32_t* dist, uint8_t* status) {
+    return guarded([&] {
+        if ((n_pairs && (!pair_a || !pair_b || !dist || !status)) || (n_weights && !weights)) throw DeviceError("null pointer");
+        check_path_table(entries, path_off, n_paths, n_weights, "path");
+        PathPool pool;
+        std::vector<uint64_t> weight(n_paths);
+        for (uint32_t p = 0; p < n_paths; p++) {
+            pool.add(entries + path_off[p], path_off[p + 1] - path_off[p]);
+            weight[p] = path_weight(pool.at(p), pool.len(p), weights);
+        }
+        std::vector<PathPair> jobs;
+        std::vector<uint64_t> where;
+        for (uint64_t q = 0; q < n_pairs; q++) {
+            if (pair_a[q] >= n_paths || pair_b[q] >= n_paths) throw DeviceError("pair " + std::to_string(q) + " names a path that does not exist");
+            if (std::max(pool.len(pair_a[q]), pool.len(pair_b[q])) > resolve_max_path())
+                throw DeviceError("a path of " + std::to_string(std::max(pool.len(pair_a[q]), pool.len(pair_b[q]))) + " entries is above the " +
+                                  std::to_string(resolve_max_path()) + " this library supports (ac_resolve_max_path)");
+            dist[q] = 0;
+            status[q] = pair_overflows(weight[pair_a[q]], weight[pair_b[q]]) ? 2 : 0;      // 2: the reference's u32 matrix could overflow — not launched
+            if (status[q] == 0) { jobs.push_back(PathPair{pair_a[q], pair_b[q]}); where.push_back(q); }
+        }
+        if (jobs.empty()) return;
+        DeviceCall call(device);
+        std::vector<uint32_t> d;
+        path_distance_batch(pool, jobs, weights, &d, nullptr);
+        for (size_t i = 0; i < jobs.size(); i++) dist[where[i]] = d[i];
+    });
+}
+static void resolve_run(const int32_t* path, const uint64_t* off, uint32_t n_seqs, const uint16_t* seq_ids, const uint32_t* consensus_weight,
+                        const uint32_t* weights, uint32_t n_weights, int device, ac_resolve** out) {
+    if (!out) throw DeviceError("null pointer");
+    *out = nullptr;
+    if (n_weights && !weights) throw DeviceError("null pointer");
+    check_path_table(path, off, n_seqs, n_weights, "path of sequence");
+    auto h = std::make_unique<ac_resolve>();
+    ResolveDeviceStats st;
+    resolve_bridges_host(path, off, n_seqs, seq_ids, consensus_weight, weights, n_weights,
+                         [&](const PathPool& pool, const std::vector<PathPair>& pairs, std::vector<uint32_t>& dist) {
+                             DeviceCall call(device);      // (only when there is something to launch)
+                             path_distance_batch(pool, pairs, weights, &dist, &st);
+                         },
+                         &h->r);
+    h->records.resize(h->r.bridges.size());
+    for (size_t b = 0; b < h->records.size(); b++) {
+        const ResolveBridge& s = h->r.bridges[b];
+        ac_bridge& d = h->records[b];
+        memset(&d, 0, sizeof d);
+        d.start = s.start; d.end = s.end; d.depth = s.depth; d.n_distinct = s.n_distinct; d.best_off = s.best_off; d.best_total = s.best_total;
+        d.first_distinct = s.first_distinct; d.best_len = s.best_len; d.status = s.status; d.conflicting = s.conflicting; d.culled = s.culled;
+        d.cull_rank = s.cull_rank;
+    }
+    ac_resolve_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = sizeof sm; sm.jobs = st.jobs; sm.jobs_not_launched = h->r.pairs_overflowing; sm.cells = st.cells; sm.largest_job_cells = st.largest_job_cells;
+    sm.launches = st.launches; sm.seconds_device = st.seconds_device;
+    *out = h.release();
+}
+int ac_resolve_bridge_paths(const int32_t* path_entries, const uint64_t* path_off, uint32_t n_seqs, const uint32_t* consensus_weight, const uint32_t* weights,
+                            uint32_t n_weights, int device, ac_resolve** out) {
+    return guarded([&] { resolve_run(path_entries, path_off, n_seqs, nullptr, consensus_weight, weights, n_weights, device, out); });
+}
+int ac_resolve_bridges(const ac_graph* g, int device, ac_resolve** out) {
+    return guarded([&] {
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+        if (n_seqs == 0 || g->g.path_off.size() != (size_t)n_seqs + 1 || !g->g.seq_len) throw DeviceError("resolve: the graph holds no paths");
+        std::vector<uint32_t> cw(n_seqs, 1);      // (a built graph carries no headers: every weight is 1, as for headers without the tag)
+        for (uint32_t s = 0; s < n_seqs && s < g->headers.size(); s++) cw[s] = consensus_weight_of(g->headers[s].c_str());
+        resolve_run(g->g.path, g->g.path_off.data(), n_seqs, g->seq_ids.data(), cw.data(), g->g.seq_len, g->g.n_unitigs, device, out);
+    });
+}
+int ac_resolve_anchors(const ac_resolve* r, const uint32_t** anchors, uint32_t* n) {
+    return guarded([&] {
+        if (!r || !anchors || !n) throw DeviceError("null pointer");
+        *anchors = r->r.anchors.data(); *n = (uint32_t)r->r.anchors.size();
+    });
+}
+int ac_resolve_bridge_records(const ac_resolve* r, const ac_bridge** bridges, uint32_t* n) {
+    return guarded([&] {
+        if (!r || !bridges || !n) throw DeviceError("null pointer");
+        *bridges = r->records.data(); *n = (uint32_t)r->records.size();
+    });
+}
+int ac_resolve_best_paths(const ac_resolve* r, const int32_t** entries, uint64_t* n_entries) {
+    return guarded([&] {
+        if (!r || !entries) throw DeviceError("null pointer");
+        *entries = r->r.best_pool.data();
+        if (n_entries) *n_entries = r->r.best_pool.size();
+    });
+}
+int ac_resolve_distinct_paths(const ac_resolve* r, const int32_t** entries, const uint64_t** path_off, const uint32_t** multiplicity, uint64_t* n_paths) {
+    return guarded([&] {
+        if (!r) throw DeviceError("null pointer");
+        if (entries) *entries = r->r.distinct.entries.data();
+        if (path_off) *path_off = r->r.distinct.off.data();
+        if (multiplicity) *multiplicity = r->r.multiplicity.data();
+        if (n_paths) *n_paths = r->r.distinct.size();
+    });
+}
+size_t ac_resolve_summary_get_sized(const ac_resolve* r, ac_resolve_summary* out, size_t out_size) {
+    if (r && out) memcpy(out, &r->summary, std::min(out_size, sizeof(ac_resolve_summary)));
+    return sizeof(ac_resolve_summary);
+}
+uint32_t ac_resolve_max_path(void) { return resolve_max_path(); }
+void ac_resolve_free(ac_resolve* r) { delete r; }
 
 // ---- read-based unitig depths of `autocycler combine --reads` (depth.rs:45-76): the k-mer table and the read tally on the device
 // (graph_depth.hip), the graph walks and the per-unitig arithmetic on the host (depth_host.cpp) ----

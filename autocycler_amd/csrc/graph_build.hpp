@@ -13,6 +13,7 @@
 
 #include "graph_types.hpp"
 #include "trim_host.hpp"
+#include "resolve_host.hpp"
 
 namespace ac {
 
@@ -185,6 +186,11 @@ struct TrimDeviceStats { double seconds_device = 0; uint64_t cells = 0; uint32_t
 void overlap_alignment_batch(const std::vector<AlignJob>& jobs, const uint32_t* weights, uint32_t max_unitigs, std::vector<AlignOut>* outs,
                              TrimDeviceStats* st);
 uint32_t trim_max_unitigs();      // largest min(max_unitigs, path length) the alignment kernels take
+// global_alignment_distance (resolve.rs:387-418) for a batch of path pairs on the device (kernels_resolve.inc); the host side of `resolve` is resolve_host.cpp.
+struct ResolveDeviceStats { double seconds_device = 0; uint64_t cells = 0, jobs = 0, largest_job_cells = 0; uint32_t launches = 0; };
+void path_distance_batch(const PathPool& pool, const std::vector<PathPair>& pairs, const uint32_t* weights, std::vector<uint32_t>* dist,
+                         ResolveDeviceStats* st);
+uint32_t resolve_max_path();      // longest path the distance kernel takes
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

@@ -379,6 +379,8 @@ void seq_expand_finish(SeqExpandJob& j) noexcept;
 //   AC_DEBUG_LAUNCH   (read once) every functor launch announced on stderr and waited for (device_rt.hpp); AC_DEBUG_ARENA: arena and copy-walk figures.
 //   AC_TRIM_BATCH_BYTES  (4 GB) ac_trim_paths / ac_overlap_alignment: bytes of bit matrices one launch of the alignment kernels may hold; the
 //                     jobs of a phase that need more run in several launches (tests: the batching path).  One job always runs, whatever its size.
+//   AC_RESOLVE_BATCH_BYTES  (1 GB) ac_path_distances / ac_resolve_bridges: bytes of scratch rows one launch of the distance kernel may hold; the
+//                     jobs that need more run in several launches (tests: the batching path).  One job always runs, whatever its size.
 // The tuning / test knobs (environment) as ONE struct, read once per process (round 6: every accessor used to call getenv on every build).
 // tests and tools/ab_knobs.py, which change the variables between the builds of one process, set AC_TUNING_FOLLOW_ENV=1 before the library
 // is first used: the struct is then read again whenever a build selects its device (under the C ABI's build lock).  The accessors below
@@ -430,6 +432,7 @@ struct Knobs {
     int multi_fragments;
     int multi_tail;
     u64 trim_batch_bytes;
+    u64 resolve_batch_bytes;
     static Knobs read() {
         Knobs k;
         k.minkey_variant = [&]() -> int { const char* e = getenv("AC_MINKEY_VARIANT"); return e ? atoi(e) : -1; }();
@@ -480,6 +483,7 @@ struct Knobs {
         k.multi_fragments = [&]() -> int { const char* e = getenv("AC_MULTI_FRAGMENTS"); return e && !strcmp(e, "bytes") ? 1 : 0; }();
         k.multi_tail = [&]() -> int { const char* e = getenv("AC_MULTI_TAIL"); return e && !strcmp(e, "replicated") ? 1 : 0; }();
         k.trim_batch_bytes = [&]() -> u64 { const char* e = getenv("AC_TRIM_BATCH_BYTES"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)4 << 30; }();
+        k.resolve_batch_bytes = [&]() -> u64 { const char* e = getenv("AC_RESOLVE_BATCH_BYTES"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)1 << 30; }();
         return k;
     }
 };

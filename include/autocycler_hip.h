@@ -374,6 +374,67 @@ int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const u
                          uint32_t max_unitigs, int skip_diagonal, int device, ac_alignment_piece* pieces, uint32_t* n_pieces);
 uint32_t ac_trim_max_unitigs(void);   /* 65536: the bit matrix of one alignment is then 537 MB */
 
+/* The compute of `autocycler resolve` (resolve.rs:44-57) up to the point where the graph is edited: the anchor unitigs
+ * (find_anchor_unitigs :134-163: the unitigs that occur exactly once, on either strand, in every sequence's path), the bridges between
+ * consecutive anchors with their best paths (create_bridges :166-190, Bridge::new :430-462), their ambiguity (determine_ambiguity
+ * :193-220) and the culling order (cull_ambiguity :285-313).  Bridge::new aligns every path of a bridge with every other one
+ * (global_alignment_distance :387-418, an n x m dynamic programme in u32); here equal paths of a bridge are merged into distinct paths with
+ * multiplicities, every unordered pair of distinct paths is one job, and the jobs of all bridges run on the device together (one wavefront
+ * per job, exact: the same u32 arithmetic).  A sequence's paths count Sequence::consensus_weight times (sequence.rs:104-109; 0 leaves the
+ * sequence out of the bridges, not out of the anchor test).
+ * The bridges come in Bridge::cmp order (resolve.rs:506-514).  best path = best_paths[best_off .. best_off + best_len), start and end anchor
+ * stripped as in the reference: the distinct path with the smallest (sum of distances to all other paths, path), paths compared as Rust
+ * compares Vec<i32>.  The bridge's distinct paths are paths [first_distinct, first_distinct + n_distinct) of ac_resolve_distinct_paths, in
+ * ascending path order, with their multiplicities (what reduce_depths, resolve.rs:261-270, subtracts).
+ * status: 0 = fine; 2 = the reference's own u32 arithmetic would overflow on this bridge (two of its paths whose weights add up to 2^32 or
+ * more, or a total at or above 2^32 - 1): reported, not guessed at, and no best path.  conflicting: the flag determine_ambiguity gives with
+ * all bridges present; culled / cull_rank: cull_ambiguity removed it as the cull_rank-th (1-based; 0 = kept).
+ * Not done here (the caller applies the kept bridges): apply_bridges, reduce_depths, merge_linear_paths.
+ * Errors (return 1, ac_last_error), never aborts: an entry that is 0 or beyond the weights, offsets that do not ascend, a path that enters a
+ * distance job with more than ac_resolve_max_path() entries, a pair that names no path. */
+typedef struct ac_resolve ac_resolve;
+typedef struct {
+    int32_t start, end;          /* signed unitig numbers of the two anchors */
+    uint32_t depth;              /* Bridge::depth: the bridge's paths, copies counted */
+    uint32_t n_distinct;
+    uint64_t best_off;
+    uint64_t best_total;         /* sum over the other paths of their distance to the best path */
+    uint64_t first_distinct;
+    uint32_t best_len, status;
+    uint32_t conflicting, culled;
+    uint32_t cull_rank, reserved;
+} ac_bridge;
+typedef struct {
+    uint64_t size;               /* the library's sizeof(ac_resolve_summary) */
+    uint64_t jobs;               /* distance jobs run on the device */
+    uint64_t jobs_not_launched;  /* pairs that would overflow (status 2) */
+    uint64_t cells;              /* matrix cells those jobs stand for */
+    uint64_t largest_job_cells;
+    uint32_t launches, reserved;
+    double seconds_device;       /* the distance kernel, by device events */
+} ac_resolve_summary;
+/* On the paths of a graph handle (a build, or ac_graph_from_gfa: weights = unitig lengths, consensus weights from the HD:Z headers; a built
+ * graph carries no headers and every sequence counts once). */
+int ac_resolve_bridges(const ac_graph*, int device, ac_resolve** out);
+/* The same on caller-supplied paths: path_entries[path_off[s] .. path_off[s + 1]) signed unitig numbers, weights[u - 1] = length of unitig u
+ * (as for ac_trim_path_slices), consensus_weight[s] per sequence or NULL (all 1). */
+int ac_resolve_bridge_paths(const int32_t* path_entries, const uint64_t* path_off, uint32_t n_seqs, const uint32_t* consensus_weight,
+                            const uint32_t* weights, uint32_t n_weights, int device, ac_resolve** out);
+int ac_resolve_anchors(const ac_resolve*, const uint32_t** anchors /* ascending unitig numbers */, uint32_t* n);
+int ac_resolve_bridge_records(const ac_resolve*, const ac_bridge** bridges, uint32_t* n);
+int ac_resolve_best_paths(const ac_resolve*, const int32_t** entries, uint64_t* n_entries /* may be NULL */);
+/* any out pointer may be NULL; path_off holds n_paths + 1 offsets */
+int ac_resolve_distinct_paths(const ac_resolve*, const int32_t** entries, const uint64_t** path_off, const uint32_t** multiplicity, uint64_t* n_paths);
+/* at most out_size bytes are written (the struct only grows at its end); returns the library's sizeof(ac_resolve_summary) */
+size_t ac_resolve_summary_get_sized(const ac_resolve*, ac_resolve_summary* out, size_t out_size);
+void ac_resolve_free(ac_resolve*);
+/* global_alignment_distance (resolve.rs:387-418) itself for a batch of pairs of the caller's paths, through the same kernel: dist[q] for
+ * paths pair_a[q], pair_b[q].  status[q]: 0 = dist[q] holds; 2 = the two paths' weights add up to 2^32 or more (the reference's matrix
+ * could overflow): not launched, dist[q] = 0. */
+int ac_path_distances(const int32_t* entries, const uint64_t* path_off, uint32_t n_paths, const uint32_t* pair_a, const uint32_t* pair_b,
+                      uint64_t n_pairs, const uint32_t* weights, uint32_t n_weights, int device, uint32_t* dist, uint8_t* status);
+uint32_t ac_resolve_max_path(void);   /* 65536 entries: the longest path a distance job takes */
+
 /* Read-based unitig depths, the --reads step of `autocycler combine` (set_read_depths, depth.rs:45-76; combine.rs:43-46 calls it): a table
  * of the consensus assembly's canonical k-mers (every k-mer of every unitig's forward sequence plus the k-mers that run across a link,
  * each occurrence counted; k odd, 11 .. 31) is built on the device, every read is streamed through it in two passes (count_one_read,
@@ -509,8 +570,10 @@ const char* ac_version(void);
  *      ac_shard_sib_words() > 0; degree buffers are ac_shard_degree_bytes() bytes; ac_shard_paths_export fails after
  *      ac_shard_finish(want & 2) (the rank's own paths were renumbered on the host: read them from the handle).
  *   6: ac_verify_report grew (checks, first_bad_junction; failed bits 2048 / 4096 / 8192).
- *   7: ac_link is two signed unitig numbers (8 bytes; it was { u32 a; u8 a_fwd; u32 b; u8 b_fwd } = 16). */
-#define AC_ABI_VERSION 7
+ *   7: ac_link is two signed unitig numbers (8 bytes; it was { u32 a; u8 a_fwd; u32 b; u8 b_fwd } = 16).
+ *   8: additions only (a caller of generation 7 runs unchanged): ac_resolve_bridges, ac_resolve_bridge_paths, ac_path_distances, the
+ *      ac_resolve_* accessors with ac_bridge and ac_resolve_summary, ac_resolve_max_path, ac_resolve_free. */
+#define AC_ABI_VERSION 8
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
