@@ -96,6 +96,21 @@ class ResolveSummary(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("size", "reserved")}
 
 
+class ClusterNode(C.Structure):      # ac_cluster_node
+    _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
+
+
+class ClusterMerge(C.Structure):      # ac_cluster_merge
+    _fields_ = [("a", C.c_uint16), ("b", C.c_uint16), ("distance", C.c_double)]
+
+
+class ClusterSummary(C.Structure):
+    _fields_ = [("n_seqs", C.c_uint32), ("launches", C.c_uint32), ("rescans", C.c_uint64), ("compares", C.c_uint64), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DepthGraph(C.Structure):      # ac_depth_graph
     _fields_ = [("seq_bytes", C.c_void_p), ("seq_begin", C.c_void_p), ("seq_len", C.c_void_p), ("n_unitigs", C.c_uint32),
                 ("links", C.c_void_p), ("n_links", C.c_uint64)]
@@ -114,7 +129,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -204,6 +219,21 @@ def load_library(path=None):
     lib.ac_resolve_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ResolveSummary), C.c_size_t]
     lib.ac_resolve_free.argtypes = [C.c_void_p]
     lib.ac_resolve_free.restype = None
+    lib.ac_cluster_max_seqs.restype = C.c_uint32
+    lib.ac_cluster_max_seqs.argtypes = []
+    lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.ac_cluster_tree_from_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cluster_tree_from_nodes.argtypes = [C.POINTER(ClusterNode), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.ac_cluster_nodes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterNode)), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    lib.ac_cluster_merges.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterMerge)), C.POINTER(C.c_uint32)]
+    lib.ac_cluster_summary_get_sized.restype = C.c_size_t
+    lib.ac_cluster_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ClusterSummary), C.c_size_t]
+    lib.ac_cluster_free.argtypes = [C.c_void_p]
+    lib.ac_cluster_free.restype = None
+    lib.ac_cluster_cut.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.ac_cluster_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.ac_cluster_containment.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p]
+    lib.ac_cluster_newick.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_begin.argtypes = [C.c_uint32, C.POINTER(DepthGraph), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_begin_handles.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_add_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
@@ -357,6 +387,28 @@ class Graph:
         h = C.c_void_p()
         _check(self._lib, self._lib.ac_resolve_bridges(self._h, device, C.byref(h)))
         return _resolve_result(self._lib, h)
+
+    def default_tip_names(self):
+        """Sequence::string_for_newick (sequence.rs:77-87) per sequence: "{id}__{filename}__{contig_name}__{length}_bp", the contig
+        name being the header up to its first space.  A built graph carries no file names or headers: both parts are empty."""
+        names = []
+        for i in range(self._lib.ac_graph_seq_count(self._h)):
+            idv, ln, fn, hd = C.c_uint16(), C.c_uint32(), C.c_char_p(), C.c_char_p()
+            _check(self._lib, self._lib.ac_graph_seq_info(self._h, C.c_uint32(i), C.byref(idv), C.byref(ln), C.byref(fn), C.byref(hd)))
+            contig = (hd.value or b"").decode().split(" ")[0]
+            names.append(f"{idv.value}__{(fn.value or b'').decode()}__{contig}__{ln.value}_bp")
+        return names
+
+    def cluster_tree(self, normalise=True, device=0, want_distances=False):
+        """pairwise_contig_distances, make_symmetrical_distances and upgma (cluster.rs:132-192, 395-480) on this graph's paths, on the device
+        in one go (ac_cluster_tree_build) -> ClusterTree, or (ClusterTree, S x S list of lists equal to pairwise_distances()) with
+        want_distances.  The tree's default tip names are default_tip_names()."""
+        S = self._lib.ac_graph_seq_count(self._h)
+        out = (C.c_double * max(S * S, 1))() if want_distances else None
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_cluster_tree_build(self._h, 1 if normalise else 0, device, out, C.byref(h)))
+        tree = ClusterTree(self._lib, h, self.default_tip_names())
+        return (tree, [[out[a * S + b] for b in range(S)] for a in range(S)]) if want_distances else tree
 
     def verify(self, seqs, device=0):
         """ac_verify_graph: the round-trip verifier on the device (decompress identity, check_links, depth, renumber order, statistics).
@@ -525,6 +577,151 @@ def resolve_bridge_paths(paths, weights, consensus_weights=None, device=0, lib_p
     h = C.c_void_p()
     _check(lib, lib.ac_resolve_bridge_paths(ent, offs, len(paths), cw, w, nw, device, C.byref(h)))
     return _resolve_result(lib, h)
+
+
+class ClusterTree:
+    """Owning handle of an ac_cluster_tree: the UPGMA tree of `autocycler cluster` (cluster.rs:395-494) and the host functions on it."""
+
+    def __init__(self, lib, handle, tip_names=None):
+        self._lib, self._h, self.tip_names = lib, handle, tip_names
+
+    def close(self):
+        if self._h:
+            self._lib.ac_cluster_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @classmethod
+    def from_nodes(cls, nodes, root, lib_path=None):
+        """ac_cluster_tree_from_nodes: nodes = [(id, left index, right index, distance)], -1 / -1 at a tip; root = index of the root."""
+        lib = load_library(lib_path)
+        arr = (ClusterNode * max(len(nodes), 1))()
+        for i, (nid, left, right, dist) in enumerate(nodes):
+            arr[i].id, arr[i].left, arr[i].right, arr[i].distance = nid, left, right, dist
+        h = C.c_void_p()
+        _check(lib, lib.ac_cluster_tree_from_nodes(arr, len(nodes), root, C.byref(h)))
+        return cls(lib, h)
+
+    def _nodes(self):
+        p, n, root = C.POINTER(ClusterNode)(), C.c_uint32(), C.c_int32()
+        _check(self._lib, self._lib.ac_cluster_nodes(self._h, C.byref(p), C.byref(n), C.byref(root)))
+        return [(p[i].id, p[i].left, p[i].right, p[i].distance) for i in range(n.value)], root.value
+
+    @property
+    def nodes(self):
+        """[(id, left, right, distance)]: a built tree has its tips first, in sequence order, then the internal nodes in merge order"""
+        return self._nodes()[0]
+
+    @property
+    def root(self):
+        return self._nodes()[1]
+
+    @property
+    def merges(self):
+        """[(a, b, distance)]: cluster ids a < b and the value get_closest_pair compared"""
+        p, n = C.POINTER(ClusterMerge)(), C.c_uint32()
+        _check(self._lib, self._lib.ac_cluster_merges(self._h, C.byref(p), C.byref(n)))
+        return [(p[i].a, p[i].b, p[i].distance) for i in range(n.value)]
+
+    @property
+    def summary(self):
+        sm = ClusterSummary()
+        assert self._lib.ac_cluster_summary_get_sized(self._h, C.byref(sm), C.sizeof(ClusterSummary)) == C.sizeof(ClusterSummary)
+        return sm.as_dict()
+
+    def _n_tips(self):
+        return sum(1 for n in self.nodes if n[1] < 0)
+
+    def cut(self, cutoff, manual=()):
+        """automatic_clustering (no manual clusters) or manual_clustering -> the clusters' node ids, ascending"""
+        manual = list(manual)
+        m = (C.c_uint16 * max(len(manual), 1))(*manual)
+        out, n = (C.c_uint16 * self._n_tips())(), C.c_uint32()
+        _check(self._lib, self._lib.ac_cluster_cut(self._h, cutoff, m, len(manual), out, C.byref(n)))
+        return list(out)[:n.value]
+
+    def assign(self, cluster_nodes, lengths):
+        """ac_cluster_assign: (cluster per tip after reorder_clusters, cluster_dist per reordered cluster); lengths: one per tip"""
+        cluster_nodes, lengths = list(cluster_nodes), list(lengths)
+        n_tips = self._n_tips()
+        if len(lengths) != n_tips:
+            raise AutocyclerError(f"{len(lengths)} lengths for {n_tips} tips")
+        cn = (C.c_uint16 * max(len(cluster_nodes), 1))(*cluster_nodes)
+        ln = (C.c_uint64 * n_tips)(*lengths)
+        of_seq, dist, nc = (C.c_uint16 * n_tips)(), (C.c_double * max(len(cluster_nodes), 1))(), C.c_uint32()
+        _check(self._lib, self._lib.ac_cluster_assign(self._h, cn, len(cluster_nodes), ln, of_seq, dist, C.byref(nc)))
+        return list(of_seq), list(dist)[:nc.value]
+
+    def newick(self, names=None, file_form=False):
+        """tree_to_newick, or with file_form the line save_tree_to_newick writes.  names: one per tip (default: the graph's
+        default_tip_names(), or the ids for a tree that came from a matrix or from nodes)"""
+        names = self.tip_names if names is None else names
+        arr = None
+        if names is not None:
+            if len(names) != self._n_tips():
+                raise AutocyclerError(f"{len(names)} names for {self._n_tips()} tips")
+            arr = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        out = C.c_void_p()
+        _check(self._lib, self._lib.ac_cluster_newick(self._h, arr, 1 if file_form else 0, C.byref(out)))
+        s = C.string_at(out.value).decode()
+        self._lib.ac_string_free(out)
+        return s
+
+
+def _double_matrix(distances):
+    n = len(distances)
+    try:
+        import numpy as np
+        if isinstance(distances, np.ndarray):
+            a = np.ascontiguousarray(distances, dtype=np.float64)
+            if a.shape != (n, n):
+                raise AutocyclerError("the distance matrix is not square")
+            return a.ctypes.data_as(C.c_void_p), n, a
+    except ImportError:
+        pass
+    if any(len(r) != n for r in distances):
+        raise AutocyclerError("the distance matrix is not square")
+    arr = (C.c_double * max(n * n, 1))(*[x for r in distances for x in r])
+    return arr, n, arr
+
+
+def cluster_tree(distances, ids, normalise=True, device=0, lib_path=None):
+    """ac_cluster_tree_from_distances: make_symmetrical_distances and upgma on the caller's asymmetric S x S matrix (lists of lists or a numpy
+    array, row a / column b = distance a vs b) and ascending sequence ids -> ClusterTree."""
+    lib = load_library(lib_path)
+    ptr, n, _keep = _double_matrix(distances)
+    ids = list(ids)
+    if len(ids) != n:
+        raise AutocyclerError(f"{len(ids)} ids for a matrix of {n} rows")
+    if any(not 0 <= i <= 0xFFFF for i in ids):
+        raise AutocyclerError("a sequence id is not a u16")
+    h = C.c_void_p()
+    _check(lib, lib.ac_cluster_tree_from_distances(ptr, (C.c_uint16 * max(n, 1))(*ids), n, 1 if normalise else 0, device, C.byref(h)))
+    return ClusterTree(lib, h)
+
+
+def max_cluster_seqs(lib_path=None):
+    """ac_cluster_max_seqs: the most sequences the merge loop takes"""
+    return load_library(lib_path).ac_cluster_max_seqs()
+
+
+def cluster_containment(distances, cluster_of_seq, n_clusters, cutoff, lib_path=None):
+    """ac_cluster_containment: ({(x, y): contain_count}, {(x, y): total_count}) over the ordered pairs of different clusters 1 .. n_clusters"""
+    lib = load_library(lib_path)
+    ptr, n, _keep = _double_matrix(distances)
+    if len(cluster_of_seq) != n:
+        raise AutocyclerError(f"{len(cluster_of_seq)} cluster numbers for a matrix of {n} rows")
+    cs = (C.c_uint16 * max(n, 1))(*cluster_of_seq)
+    cc, tc = (C.c_uint64 * max(n_clusters * n_clusters, 1))(), (C.c_uint64 * max(n_clusters * n_clusters, 1))()
+    _check(lib, lib.ac_cluster_containment(ptr, n, cs, n_clusters, cutoff, cc, tc))
+    pairs = [(x, y) for x in range(1, n_clusters + 1) for y in range(1, n_clusters + 1) if x != y]
+    at = lambda x, y: (x - 1) * n_clusters + (y - 1)
+    return {p: cc[at(*p)] for p in pairs}, {p: tc[at(*p)] for p in pairs}
 
 
 class ReadDepth:

@@ -1,4 +1,4 @@
-// C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, resolve, read depths, the
+// C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, resolve, cluster, read depths, the
 // verifier, decompress, the GFA reload, and the self-tests of the device primitives.
 #include <algorithm>
 #include <cstring>
@@ -235,6 +235,136 @@ size_t ac_resolve_summary_get_sized(const ac_resolve* r, ac_resolve_summary* out
 }
 uint32_t ac_resolve_max_path(void) { return resolve_max_path(); }
 void ac_resolve_free(ac_resolve* r) { delete r; }
+
+// ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
+// from it on the host (cluster_host.cpp).  Scoring the clusters and writing them stays with the caller ----
+struct ac_cluster_tree {
+    ClusterTree t;
+    std::vector<ac_cluster_node> nodes;
+    std::vector<ac_cluster_merge> merges;
+    ac_cluster_summary summary;
+    void publish(uint32_t n_seqs, const ClusterDeviceStats& st) {
+        nodes.resize(t.nodes.size());
+        for (size_t i = 0; i < nodes.size(); i++) {
+            memset(&nodes[i], 0, sizeof nodes[i]);
+            nodes[i].id = t.nodes[i].id; nodes[i].left = t.nodes[i].left; nodes[i].right = t.nodes[i].right; nodes[i].distance = t.nodes[i].distance;
+        }
+        merges.resize(t.merges.size());
+        for (size_t i = 0; i < merges.size(); i++) {
+            memset(&merges[i], 0, sizeof merges[i]);
+            merges[i].a = t.merges[i].a; merges[i].b = t.merges[i].b; merges[i].distance = t.merges[i].distance;
+        }
+        memset(&summary, 0, sizeof summary);
+        summary.n_seqs = n_seqs; summary.launches = st.launches; summary.rescans = st.rescans; summary.compares = st.compares; summary.seconds = st.seconds;
+    }
+};
+static void cluster_check_count(uint32_t n) {
+    if (n > cluster_max_seqs())
+        throw DeviceError("cluster: " + std::to_string(n) + " sequences are above the " + std::to_string(cluster_max_seqs()) + " this library supports (ac_cluster_max_seqs)");
+}
+int ac_cluster_tree_from_distances(const double* asym, const uint16_t* ids, uint32_t n, int normalise, int device, ac_cluster_tree** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer");
+        *out = nullptr;
+        cluster_check_ids(ids, n);
+        cluster_check_count(n);
+        if (!asym) throw DeviceError("null pointer");
+        auto h = std::make_unique<ac_cluster_tree>();
+        std::vector<ClusterRowMerge> merges;
+        ClusterDeviceStats st;
+        {
+            DeviceCall call(device);
+            cluster_merges_device(asym, n, &merges, &st);
+        }
+        cluster_tree_from_merges(ids, n, merges, normalise != 0, &h->t);
+        h->publish(n, st);
+        *out = h.release();
+    });
+}
+int ac_cluster_tree_build(const ac_graph* g, int normalise, int device, double* asym_out, ac_cluster_tree** out) {
+    return guarded([&] {
+        if (!g || !out) throw DeviceError("null pointer");
+        *out = nullptr;
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const uint32_t n = (uint32_t)g->seq_ids.size();
+        if (n == 0 || g->g.path_off.size() != (size_t)n + 1 || !g->g.seq_len) throw DeviceError("cluster: the graph holds no paths");
+        cluster_check_ids(g->seq_ids.data(), n);
+        cluster_check_count(n);
+        auto h = std::make_unique<ac_cluster_tree>();
+        std::vector<ClusterRowMerge> merges;
+        ClusterDeviceStats st;
+        {
+            DeviceCall call(device);
+            cluster_merges_graph_device(g->g, n, asym_out, &merges, &st);
+        }
+        cluster_tree_from_merges(g->seq_ids.data(), n, merges, normalise != 0, &h->t);
+        h->publish(n, st);
+        *out = h.release();
+    });
+}
+int ac_cluster_tree_from_nodes(const ac_cluster_node* nodes, uint32_t n_nodes, int32_t root, ac_cluster_tree** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer");
+        *out = nullptr;
+        if (!nodes && n_nodes) throw DeviceError("null pointer");
+        std::vector<ClusterNode> in(n_nodes);
+        for (uint32_t i = 0; i < n_nodes; i++) in[i] = ClusterNode{nodes[i].id, nodes[i].left, nodes[i].right, nodes[i].distance};
+        auto h = std::make_unique<ac_cluster_tree>();
+        cluster_tree_from_nodes(in.data(), n_nodes, root, &h->t);
+        h->publish((uint32_t)h->t.tips.size(), ClusterDeviceStats());
+        *out = h.release();
+    });
+}
+int ac_cluster_nodes(const ac_cluster_tree* t, const ac_cluster_node** nodes, uint32_t* n_nodes, int32_t* root) {
+    return guarded([&] {
+        if (!t || !nodes || !n_nodes) throw DeviceError("null pointer");
+        *nodes = t->nodes.data(); *n_nodes = (uint32_t)t->nodes.size();
+        if (root) *root = t->t.root;
+    });
+}
+int ac_cluster_merges(const ac_cluster_tree* t, const ac_cluster_merge** merges, uint32_t* n_merges) {
+    return guarded([&] {
+        if (!t || !merges || !n_merges) throw DeviceError("null pointer");
+        *merges = t->merges.data(); *n_merges = (uint32_t)t->merges.size();
+    });
+}
+size_t ac_cluster_summary_get_sized(const ac_cluster_tree* t, ac_cluster_summary* out, size_t out_size) {
+    if (t && out) memcpy(out, &t->summary, std::min(out_size, sizeof(ac_cluster_summary)));
+    return sizeof(ac_cluster_summary);
+}
+void ac_cluster_free(ac_cluster_tree* t) { delete t; }
+uint32_t ac_cluster_max_seqs(void) { return cluster_max_seqs(); }
+int ac_cluster_cut(const ac_cluster_tree* t, double cutoff, const uint16_t* manual, uint32_t n_manual, uint16_t* nodes_out, uint32_t* n_out) {
+    return guarded([&] {
+        if (!t || !nodes_out || !n_out) throw DeviceError("null pointer");
+        const std::vector<uint16_t> c = cluster_cut(t->t, cutoff, manual, n_manual);
+        std::copy(c.begin(), c.end(), nodes_out);      // (disjoint subtrees: never more than there are tips)
+        *n_out = (uint32_t)c.size();
+    });
+}
+int ac_cluster_assign(const ac_cluster_tree* t, const uint16_t* cluster_nodes, uint32_t n, const uint64_t* seq_len, uint16_t* cluster_of_seq,
+                      double* cluster_dist, uint32_t* n_clusters) {
+    return guarded([&] {
+        if (!t) throw DeviceError("null pointer");
+        const uint32_t c = cluster_assign(t->t, cluster_nodes, n, seq_len, cluster_of_seq, cluster_dist);
+        if (n_clusters) *n_clusters = c;
+    });
+}
+int ac_cluster_containment(const double* asym, uint32_t n, const uint16_t* cluster_of_seq, uint32_t n_clusters, double cutoff,
+                           uint64_t* contain_count, uint64_t* total_count) {
+    return guarded([&] { cluster_containment(asym, n, cluster_of_seq, n_clusters, cutoff, contain_count, total_count); });
+}
+int ac_cluster_newick(const ac_cluster_tree* t, const char* const* tip_names, int file_form, char** out) {
+    return guarded([&] {
+        if (!t || !out) throw DeviceError("null pointer");
+        *out = nullptr;
+        const std::string s = cluster_newick(t->t, tip_names, file_form != 0);
+        char* p = (char*)malloc(s.size() + 1);
+        if (!p) throw DeviceError("out of memory");
+        memcpy(p, s.c_str(), s.size() + 1);
+        *out = p;
+    });
+}
 
 // ---- read-based unitig depths of `autocycler combine --reads` (depth.rs:45-76): the k-mer table and the read tally on the device
 // (graph_depth.hip), the graph walks and the per-unitig arithmetic on the host (depth_host.cpp) ----

@@ -14,6 +14,7 @@
 #include "graph_types.hpp"
 #include "trim_host.hpp"
 #include "resolve_host.hpp"
+#include "cluster_host.hpp"
 
 namespace ac {
 
@@ -191,6 +192,13 @@ struct ResolveDeviceStats { double seconds_device = 0; uint64_t cells = 0, jobs 
 void path_distance_batch(const PathPool& pool, const std::vector<PathPair>& pairs, const uint32_t* weights, std::vector<uint32_t>* dist,
                          ResolveDeviceStats* st);
 uint32_t resolve_max_path();      // longest path the distance kernel takes
+// upgma's merge loop (cluster.rs:395-480) on the device (kernels_cluster.inc): the n - 1 merges, rows = sequences in ascending id order; the
+// tree and everything after it is cluster_host.cpp.  asym: the n x n matrix of pairwise_contig_distances on the host; the graph form
+// computes it on the device in the same arena session (asym_out, when given, receives what pairwise_distances_device writes).
+struct ClusterDeviceStats { double seconds = 0; uint64_t rescans = 0, compares = 0; uint32_t launches = 0; };
+void cluster_merges_device(const double* asym, uint32_t n, std::vector<ClusterRowMerge>* merges, ClusterDeviceStats* st);
+void cluster_merges_graph_device(const FinalGraph& g, uint32_t n_seqs, double* asym_out, std::vector<ClusterRowMerge>* merges, ClusterDeviceStats* st);
+uint32_t cluster_max_seqs();      // most sequences the merge loop takes
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

@@ -276,7 +276,8 @@ struct PairLenFunctor {       // thread t of pair p = t / 64 takes the words lan
         if (lane == 0) ab[pair] = sum;
     }
 };
-void pairwise_distances_device(const FinalGraph& g, uint32_t n_seqs, double* out) {
+// ab[a * n_seqs + b] = total length of the unitigs the paths of a and b share, left on the device (starts an arena session of its own)
+static DBuf<u64> pair_lengths_device(const FinalGraph& g, uint32_t n_seqs) {
     if (n_seqs == 0 || g.path_off.size() != (size_t)n_seqs + 1) throw DeviceError("pairwise distances: the graph holds no paths");
     const u32 U = g.n_unitigs;
     const u64 n_ent = g.n_path, words = ((u64)U + 63) / 64;
@@ -290,6 +291,10 @@ void pairwise_distances_device(const FinalGraph& g, uint32_t n_seqs, double* out
     bits.fill_bytes(0); ab.fill_bytes(0);
     launch(n_ent, PathBitsFunctor{d_path.ptr(), d_off.ptr(), n_seqs, n_ent, words, (u32*)bits.ptr()});
     launch_full((u64)n_seqs * n_seqs * 64, PairLenFunctor{bits.ptr(), words, d_len.ptr(), n_seqs, ab.ptr()});
+    return ab;
+}
+void pairwise_distances_device(const FinalGraph& g, uint32_t n_seqs, double* out) {
+    DBuf<u64> ab = pair_lengths_device(g, n_seqs);
     std::vector<u64> h = to_host(ab, (size_t)n_seqs * n_seqs);
     for (u32 a = 0; a < n_seqs; a++) {
         double a_len = (double)(uint32_t)h[(size_t)a * n_seqs + a];        // |U_a ∩ U_a|; the reference sums a_len in u32

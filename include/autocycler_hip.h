@@ -435,6 +435,74 @@ int ac_path_distances(const int32_t* entries, const uint64_t* path_off, uint32_t
                       uint64_t n_pairs, const uint32_t* weights, uint32_t n_weights, int device, uint32_t* dist, uint8_t* status);
 uint32_t ac_resolve_max_path(void);   /* 65536 entries: the longest path a distance job takes */
 
+/* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
+ * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
+ * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
+ * Arithmetic.  The reference sums the original distances of all member pairs in HashSet order, which differs from process to process, so
+ * its means are only defined up to the rounding of an f64 sum in some order.  The library fixes one order: per cluster pair it keeps
+ * sum(A, X); at the start sum(i, j) = max(d(i,j), d(j,i)) (make_symmetrical_distances :177-192) and that is the compared value; merging
+ * a < b sets sum(a, X) = sum(a, X) + sum(b, X) and compares sum(a, X) / (double)(size(a u b) * size(X)).  Mathematically the reference's
+ * mean; bit for bit the reference's result wherever the sums are exact (e.g. distances that are multiples of 2^-16, S <= 300).
+ * Among equal minima the lexicographically smallest (a, b) wins, as in get_closest_pair; the merged cluster keeps id a; its node gets the
+ * next number after the largest sequence id; left = the node of a, right = the node of b, distance = compared value / 2.
+ * normalise != 0: normalise_tree (:483-494) afterwards, on the host.
+ * Errors (return 1, ac_last_error), all found before anything is launched except the last: n == 0; ids that do not ascend strictly;
+ * largest id + n - 1 > 65535 (the reference's u16 node counter would overflow); n > ac_cluster_max_seqs(); a distance that is NaN,
+ * infinite or negative (a device flag, read once after the loop).
+ * Not done here (the caller's): refine_auto_clusters / score_clustering / clustering_metrics, the QC verdicts, set_min_assemblies, the
+ * per-cluster GFAs, the TSV / YAML / PHYLIP files. */
+typedef struct ac_cluster_tree ac_cluster_tree;
+typedef struct {
+    uint16_t id;                 /* a tip: the sequence id; an internal node: largest id + 1, + 2, ... in merge order */
+    int32_t left, right;         /* indices into the node array; -1 at a tip */
+    double distance;             /* from the node to the tips (TreeNode::distance) */
+} ac_cluster_node;
+typedef struct {
+    uint16_t a, b;               /* cluster ids, a < b */
+    double distance;             /* the value get_closest_pair compared (twice the node's distance before normalisation) */
+} ac_cluster_merge;
+typedef struct {
+    uint32_t n_seqs, launches;
+    uint64_t rescans;            /* cache rows scanned again after a merge */
+    uint64_t compares;           /* cache rows that only compared the new column */
+    double seconds;              /* the merge loop alone, by device events */
+} ac_cluster_summary;
+/* pairwise_contig_distances, make_symmetrical_distances and upgma on the paths of a graph handle; the matrix is computed and consumed on
+ * the device in one session.  asym_out (S x S doubles, or NULL) receives exactly what ac_pairwise_distances writes. */
+int ac_cluster_tree_build(const ac_graph*, int normalise, int device, double* asym_out, ac_cluster_tree** out);
+/* The same from the caller's asymmetric matrix (row-major, asym[a * n + b] = distance a vs b) and ascending sequence ids. */
+int ac_cluster_tree_from_distances(const double* asym, const uint16_t* ids, uint32_t n, int normalise, int device, ac_cluster_tree** out);
+/* A tree the caller already holds (any node order; checked to be one binary tree with distinct ids).  No device.  "Tip order" below is
+ * the order of the tips in the node array. */
+int ac_cluster_tree_from_nodes(const ac_cluster_node* nodes, uint32_t n_nodes, int32_t root, ac_cluster_tree** out);
+/* A built tree: the tips first, in sequence order, then the internal nodes in merge order (the root last). */
+int ac_cluster_nodes(const ac_cluster_tree*, const ac_cluster_node** nodes, uint32_t* n_nodes, int32_t* root);
+int ac_cluster_merges(const ac_cluster_tree*, const ac_cluster_merge** merges, uint32_t* n_merges);   /* none for a from_nodes tree */
+/* at most out_size bytes are written; returns the library's sizeof(ac_cluster_summary) */
+size_t ac_cluster_summary_get_sized(const ac_cluster_tree*, ac_cluster_summary* out, size_t out_size);
+void ac_cluster_free(ac_cluster_tree*);
+uint32_t ac_cluster_max_seqs(void);   /* 16384: the loop keeps three S x S f64 arrays on the device, 6.4 GB at this size */
+/* automatic_clustering (n_manual == 0, cluster.rs:219-226) or manual_clustering (:228-237, with check_consistency :260-271: nested manual
+ * clusters are an error here, not an exit): the node ids of the clusters, ascending, into nodes_out (room for as many as the tree has
+ * tips).  A node is a cluster when distance <= cutoff / 2 (inclusive) and nothing below it is manual (collect_clusters :239-247). */
+int ac_cluster_cut(const ac_cluster_tree*, double cutoff, const uint16_t* manual, uint32_t n_manual, uint16_t* nodes_out, uint32_t* n_out);
+/* The first half of qc_clusters (cluster.rs:522-546): cluster k + 1 = the tips under node cluster_nodes[k] (assign_cluster_to_node
+ * :633-642), then reorder_clusters (:882-903: median sequence length descending — median_usize, misc.rs:423-430 — old number ascending on
+ * ties).  seq_len and cluster_of_seq have one entry per tip, in tip order; a tip under none of the nodes gets 0.  cluster_dist (n entries)
+ * [c - 1] = max_pairwise_distance (:208-217) = 2 * distance of the node behind the reordered cluster c; -1 for a number no sequence
+ * carries.  n_clusters (may be NULL): the largest cluster number in use.  An id that is not in the tree is an error. */
+int ac_cluster_assign(const ac_cluster_tree*, const uint16_t* cluster_nodes, uint32_t n, const uint64_t* seq_len, uint16_t* cluster_of_seq,
+                      double* cluster_dist, uint32_t* n_clusters);
+/* The two counts of cluster_is_contained_in_another (cluster.rs:705-717) for every ordered pair of different clusters x, y at
+ * [(x - 1) * n_clusters + (y - 1)]: total = pairs (sequence of x, sequence of y), contain = those with d(a,b) < d(b,a) and d(a,b) < cutoff.
+ * A host loop, O(S^2) once.  Sequences of cluster 0 take no part. */
+int ac_cluster_containment(const double* asym, uint32_t n, const uint16_t* cluster_of_seq, uint32_t n_clusters, double cutoff,
+                           uint64_t* contain_count, uint64_t* total_count);
+/* tree_to_newick (cluster.rs:381-392; file_form = 0) or the line save_tree_to_newick writes (:363-378; file_form = 1: with the
+ * "(...:root_length);" wrapper when the root's distance is below 0.5, and the newline).  Numbers as Rust's `{}` prints an f64.  tip_names:
+ * one per tip in tip order (Sequence::string_for_newick), or NULL (the ids).  Free *out with ac_string_free. */
+int ac_cluster_newick(const ac_cluster_tree*, const char* const* tip_names, int file_form, char** out);
+
 /* Read-based unitig depths, the --reads step of `autocycler combine` (set_read_depths, depth.rs:45-76; combine.rs:43-46 calls it): a table
  * of the consensus assembly's canonical k-mers (every k-mer of every unitig's forward sequence plus the k-mers that run across a link,
  * each occurrence counted; k odd, 11 .. 31) is built on the device, every read is streamed through it in two passes (count_one_read,
@@ -572,8 +640,11 @@ const char* ac_version(void);
  *   6: ac_verify_report grew (checks, first_bad_junction; failed bits 2048 / 4096 / 8192).
  *   7: ac_link is two signed unitig numbers (8 bytes; it was { u32 a; u8 a_fwd; u32 b; u8 b_fwd } = 16).
  *   8: additions only (a caller of generation 7 runs unchanged): ac_resolve_bridges, ac_resolve_bridge_paths, ac_path_distances, the
- *      ac_resolve_* accessors with ac_bridge and ac_resolve_summary, ac_resolve_max_path, ac_resolve_free. */
-#define AC_ABI_VERSION 8
+ *      ac_resolve_* accessors with ac_bridge and ac_resolve_summary, ac_resolve_max_path, ac_resolve_free.
+ *   9: additions only: ac_cluster_tree_build, ac_cluster_tree_from_distances, ac_cluster_tree_from_nodes, ac_cluster_nodes,
+ *      ac_cluster_merges, ac_cluster_summary_get_sized, ac_cluster_cut, ac_cluster_assign, ac_cluster_containment, ac_cluster_newick,
+ *      ac_cluster_max_seqs, ac_cluster_free with ac_cluster_node, ac_cluster_merge and ac_cluster_summary. */
+#define AC_ABI_VERSION 9
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
