@@ -111,6 +111,31 @@ class ClusterSummary(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ClusterQcRecord(C.Structure):      # ac_cluster_qc_record
+    _fields_ = [("node", C.c_uint16), ("container", C.c_uint16), ("size", C.c_uint32), ("assembly_count", C.c_uint32), ("fail", C.c_uint32),
+                ("trusted", C.c_uint32), ("reserved", C.c_uint32), ("median_length", C.c_uint64), ("cluster_dist", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ClusteringMetrics(C.Structure):      # ac_clustering_metrics
+    _fields_ = [(n, C.c_uint32) for n in ("pass_cluster_count", "fail_cluster_count", "pass_contig_count", "fail_contig_count")] + \
+               [(n, C.c_double) for n in ("pass_contig_fraction", "fail_contig_fraction", "cluster_balance_score", "cluster_tightness_score",
+                                          "overall_clustering_score")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ClusterQcSummary(C.Structure):      # ac_cluster_qc_summary
+    _fields_ = [(n, C.c_uint32) for n in ("n_seqs", "n_clusters", "rounds", "evaluations", "pair_batches", "launches", "readbacks", "reserved")] + \
+               [(n, C.c_uint64) for n in ("alternatives", "node_pairs", "bytes_read_back")] + [("seconds", C.c_double), ("start_score", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class DepthGraph(C.Structure):      # ac_depth_graph
     _fields_ = [("seq_bytes", C.c_void_p), ("seq_begin", C.c_void_p), ("seq_len", C.c_void_p), ("n_unitigs", C.c_uint32),
                 ("links", C.c_void_p), ("n_links", C.c_uint64)]
@@ -129,7 +154,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -234,6 +259,21 @@ def load_library(path=None):
     lib.ac_cluster_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     lib.ac_cluster_containment.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p]
     lib.ac_cluster_newick.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    qc_in = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint32]
+    lib.ac_cluster_generate.argtypes = qc_in + [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cluster_qc_nodes.argtypes = qc_in + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cluster_qc_clusters.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_uint32)]
+    lib.ac_cluster_qc_assignment.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.c_uint32)]
+    lib.ac_cluster_qc_records.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterQcRecord)), C.POINTER(C.c_uint32)]
+    lib.ac_cluster_qc_metrics.argtypes = [C.c_void_p, C.POINTER(ClusteringMetrics)]
+    lib.ac_cluster_qc_trace.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_double)),
+                                        C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+    lib.ac_cluster_qc_summary_get_sized.restype = C.c_size_t
+    lib.ac_cluster_qc_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ClusterQcSummary), C.c_size_t]
+    lib.ac_cluster_qc_free.argtypes = [C.c_void_p]
+    lib.ac_cluster_qc_free.restype = None
+    lib.ac_cluster_min_assemblies.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.ac_cluster_seq_inputs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     lib.ac_depth_begin.argtypes = [C.c_uint32, C.POINTER(DepthGraph), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_begin_handles.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_depth_add_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
@@ -398,6 +438,14 @@ class Graph:
             contig = (hd.value or b"").decode().split(" ")[0]
             names.append(f"{idv.value}__{(fn.value or b'').decode()}__{contig}__{ln.value}_bp")
         return names
+
+    def cluster_inputs(self):
+        """ac_cluster_seq_inputs: what ClusterTree.generate / qc take per sequence, from the file names and headers of a graph loaded from a
+        GFA -> {"seq_len", "assembly", "cluster_weight", "trusted": one list each, "n_assemblies"}"""
+        n = self._lib.ac_graph_seq_count(self._h)
+        ln, asm, wt, tr, f = (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_uint8 * max(n, 1))(), C.c_uint32()
+        _check(self._lib, self._lib.ac_cluster_seq_inputs(self._h, ln, asm, wt, tr, C.byref(f)))
+        return {"seq_len": list(ln)[:n], "assembly": list(asm)[:n], "cluster_weight": list(wt)[:n], "trusted": list(tr)[:n], "n_assemblies": f.value}
 
     def cluster_tree(self, normalise=True, device=0, want_distances=False):
         """pairwise_contig_distances, make_symmetrical_distances and upgma (cluster.rs:132-192, 395-480) on this graph's paths, on the device
@@ -657,6 +705,39 @@ class ClusterTree:
         _check(self._lib, self._lib.ac_cluster_assign(self._h, cn, len(cluster_nodes), ln, of_seq, dist, C.byref(nc)))
         return list(of_seq), list(dist)[:nc.value]
 
+    def _qc_inputs(self, distances, seq_len, assembly, cluster_weight, trusted):
+        ptr, n, keep = _double_matrix(distances)
+        arrays = []
+        for name, values, ctype in (("seq_len", seq_len, C.c_uint64), ("assembly", assembly, C.c_uint32), ("cluster_weight", cluster_weight, C.c_uint32),
+                                    ("trusted", trusted, C.c_uint8)):
+            values = [int(v) for v in values]
+            if len(values) != n:
+                raise AutocyclerError(f"{len(values)} entries of {name} for a matrix of {n} rows")
+            arrays.append((ctype * max(n, 1))(*values))
+        return ptr, n, keep, arrays
+
+    def generate(self, distances, seq_len, assembly, cluster_weight, trusted, cutoff, min_assemblies, manual=(), device=0):
+        """ac_cluster_generate: generate_clusters (cluster.rs:497-508) -> ClusterQC.  distances: the S x S asymmetric matrix (rows in tip
+        order); the four lists: one entry per tip (Graph.cluster_inputs()); manual: node ids, or empty for the cut at `cutoff` refined by
+        refine_auto_clusters."""
+        ptr, n, _keep, (ln, asm, wt, tr) = self._qc_inputs(distances, seq_len, assembly, cluster_weight, trusted)
+        manual = list(manual)
+        m = (C.c_uint16 * max(len(manual), 1))(*manual)
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_cluster_generate(self._h, ptr, n, ln, asm, wt, tr, cutoff, min_assemblies, m, len(manual), device, C.byref(h)))
+        return ClusterQC(self._lib, h)
+
+    def qc(self, cluster_nodes, distances, seq_len, assembly, cluster_weight, trusted, cutoff, min_assemblies, manual=(), device=0):
+        """ac_cluster_qc_nodes: qc_clusters (cluster.rs:511-570) and clustering_metrics on the given node list, without refinement -> ClusterQC"""
+        ptr, n, _keep, (ln, asm, wt, tr) = self._qc_inputs(distances, seq_len, assembly, cluster_weight, trusted)
+        manual, cluster_nodes = list(manual), list(cluster_nodes)
+        m = (C.c_uint16 * max(len(manual), 1))(*manual)
+        cn = (C.c_uint16 * max(len(cluster_nodes), 1))(*cluster_nodes)
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_cluster_qc_nodes(self._h, ptr, n, ln, asm, wt, tr, cutoff, min_assemblies, cn, len(cluster_nodes), m, len(manual),
+                                                        device, C.byref(h)))
+        return ClusterQC(self._lib, h)
+
     def newick(self, names=None, file_form=False):
         """tree_to_newick, or with file_form the line save_tree_to_newick writes.  names: one per tip (default: the graph's
         default_tip_names(), or the ids for a tree that came from a matrix or from nodes)"""
@@ -671,6 +752,48 @@ class ClusterTree:
         s = C.string_at(out.value).decode()
         self._lib.ac_string_free(out)
         return s
+
+
+class ClusterQC:
+    """The result of ClusterTree.generate / ClusterTree.qc (an ac_cluster_qc, read out once): clusters = the node ids; cluster_of_seq = the
+    reordered cluster number per tip; records = one dict per reordered cluster (node, container, size, assembly_count, fail, trusted,
+    median_length, cluster_dist; fail bits 1 = not in manual clusters, 2 = too few assemblies, 4 = contained); metrics = ClusteringMetrics;
+    trace = per refinement round {"scores": [...], "accepted": [...]} in split_clusters' order; summary = the device schedule."""
+
+    def __init__(self, lib, h):
+        try:
+            p16, n = C.POINTER(C.c_uint16)(), C.c_uint32()
+            _check(lib, lib.ac_cluster_qc_clusters(h, C.byref(p16), C.byref(n)))
+            self.clusters = [p16[i] for i in range(n.value)]
+            _check(lib, lib.ac_cluster_qc_assignment(h, C.byref(p16), C.byref(n)))
+            self.cluster_of_seq = [p16[i] for i in range(n.value)]
+            pr = C.POINTER(ClusterQcRecord)()
+            _check(lib, lib.ac_cluster_qc_records(h, C.byref(pr), C.byref(n)))
+            self.records = [pr[i].as_dict() for i in range(n.value)]
+            m = ClusteringMetrics()
+            _check(lib, lib.ac_cluster_qc_metrics(h, C.byref(m)))
+            self.metrics = m.as_dict()
+            pa, nr, ps, pacc, ns = C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint8)(), C.c_uint64()
+            _check(lib, lib.ac_cluster_qc_trace(h, C.byref(pa), C.byref(nr), C.byref(ps), C.byref(pacc), C.byref(ns)))
+            self.trace, at = [], 0
+            for r in range(nr.value):
+                self.trace.append({"scores": [ps[at + i] for i in range(pa[r])], "accepted": [bool(pacc[at + i]) for i in range(pa[r])]})
+                at += pa[r]
+            assert at == ns.value
+            sm = ClusterQcSummary()
+            assert lib.ac_cluster_qc_summary_get_sized(h, C.byref(sm), C.sizeof(ClusterQcSummary)) == C.sizeof(ClusterQcSummary)
+            self.summary = sm.as_dict()
+        finally:
+            lib.ac_cluster_qc_free(h)
+
+
+def cluster_min_assemblies(assembly, lib_path=None):
+    """ac_cluster_min_assemblies: set_min_assemblies (cluster.rs:645-661) for the dense assembly indices of the sequences"""
+    lib = load_library(lib_path)
+    assembly = [int(a) for a in assembly]
+    out = C.c_uint32()
+    _check(lib, lib.ac_cluster_min_assemblies((C.c_uint32 * max(len(assembly), 1))(*assembly), len(assembly), C.byref(out)))
+    return out.value
 
 
 def _double_matrix(distances):

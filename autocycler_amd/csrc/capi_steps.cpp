@@ -237,7 +237,7 @@ uint32_t ac_resolve_max_path(void) { return resolve_max_path(); }
 void ac_resolve_free(ac_resolve* r) { delete r; }
 
 // ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
-// from it on the host (cluster_host.cpp).  Scoring the clusters and writing them stays with the caller ----
+// from it on the host (cluster_host.cpp); the QC verdicts, scores and refinement further down.  Writing the clusters stays with the caller ----
 struct ac_cluster_tree {
     ClusterTree t;
     std::vector<ac_cluster_node> nodes;
@@ -363,6 +363,147 @@ int ac_cluster_newick(const ac_cluster_tree* t, const char* const* tip_names, in
         if (!p) throw DeviceError("out of memory");
         memcpy(p, s.c_str(), s.size() + 1);
         *out = p;
+    });
+}
+
+// ---- `autocycler cluster` after the tree: generate_clusters / qc_clusters / clustering_metrics / refine_auto_clusters.  The containment
+// test and the verdict chain of every alternative of a round on the device (kernels_cluster_qc.inc), everything else on the host
+// (cluster_qc_host.cpp) ----
+struct ac_cluster_qc {
+    ClusterQcResult r;
+    std::vector<ac_cluster_qc_record> records;
+    ac_clustering_metrics metrics;
+    ac_cluster_qc_summary summary;
+    void publish(uint32_t n_seqs, bool refined, const ClusterQcDeviceStats& st) {
+        records.resize(r.records.size());
+        for (size_t i = 0; i < records.size(); i++) {
+            const ClusterQcRecord& x = r.records[i];
+            memset(&records[i], 0, sizeof records[i]);
+            records[i].node = x.node; records[i].container = x.container; records[i].size = x.size; records[i].assembly_count = x.assembly_count;
+            records[i].fail = x.fail; records[i].trusted = x.trusted; records[i].median_length = x.median; records[i].cluster_dist = x.cluster_dist;
+        }
+        memset(&metrics, 0, sizeof metrics);
+        metrics.pass_cluster_count = r.metrics.pass_cluster_count; metrics.fail_cluster_count = r.metrics.fail_cluster_count;
+        metrics.pass_contig_count = r.metrics.pass_contig_count; metrics.fail_contig_count = r.metrics.fail_contig_count;
+        metrics.pass_contig_fraction = r.metrics.pass_contig_fraction; metrics.fail_contig_fraction = r.metrics.fail_contig_fraction;
+        metrics.cluster_balance_score = r.metrics.cluster_balance_score; metrics.cluster_tightness_score = r.metrics.cluster_tightness_score;
+        metrics.overall_clustering_score = r.metrics.overall_clustering_score;
+        memset(&summary, 0, sizeof summary);
+        summary.n_seqs = n_seqs; summary.n_clusters = (uint32_t)records.size(); summary.rounds = refined ? (uint32_t)r.round_alternatives.size() : 0;
+        summary.evaluations = st.evaluations; summary.pair_batches = st.pair_batches; summary.launches = st.launches; summary.readbacks = st.readbacks;
+        summary.alternatives = st.alternatives; summary.node_pairs = st.pairs_counted; summary.bytes_read_back = st.bytes_read_back;
+        summary.seconds = st.seconds; summary.start_score = r.start_score;
+    }
+};
+// the checks both entries share, all before a device is touched; returns the indexed tree
+static void cluster_qc_prologue(const ac_cluster_tree* t, const double* asym, uint32_t n, const uint64_t* seq_len, const uint32_t* assembly,
+                                const uint32_t* cluster_weight, const uint8_t* trusted, double cutoff, const uint16_t* manual, uint32_t n_manual,
+                                ac_cluster_qc** out, ClusterQcIndex* ix) {
+    if (!out) throw DeviceError("null pointer");
+    *out = nullptr;
+    if (!t || (n_manual && !manual) || (!n_manual && !asym)) throw DeviceError("null pointer");
+    cluster_check_count(n);
+    ClusterSeqInputs in{seq_len, assembly, cluster_weight, trusted, n, 0};
+    if (n && (!seq_len || !assembly || !cluster_weight || !trusted)) throw DeviceError("null pointer");
+    in.n_assemblies = cluster_assembly_count_checked(assembly, n);
+    cluster_qc_index(t->t, in, ix);
+    if (n_manual) (void)cluster_cut(t->t, cutoff, manual, n_manual);      // check_consistency: nested manual clusters
+}
+int ac_cluster_generate(const ac_cluster_tree* t, const double* asym, uint32_t n, const uint64_t* seq_len, const uint32_t* assembly,
+                        const uint32_t* cluster_weight, const uint8_t* trusted, double cutoff, uint32_t min_assemblies,
+                        const uint16_t* manual, uint32_t n_manual, int device, ac_cluster_qc** out) {
+    return guarded([&] {
+        ClusterQcIndex ix;
+        cluster_qc_prologue(t, asym, n, seq_len, assembly, cluster_weight, trusted, cutoff, manual, n_manual, out, &ix);
+        auto h = std::make_unique<ac_cluster_qc>();
+        ClusterQcDeviceStats st;
+        if (n_manual) cluster_generate_host(ix, cutoff, manual, n_manual, min_assemblies, ClusterQcEvaluate(), &h->r);
+        else {
+            DeviceCall call(device);
+            cluster_qc_device(asym, n, ix.dfs_tip.data(), cutoff, [&](const ClusterQcEvaluate& ev) { cluster_generate_host(ix, cutoff, nullptr, 0, min_assemblies, ev, &h->r); }, &st);
+        }
+        h->publish(n, n_manual == 0, st);
+        *out = h.release();
+    });
+}
+int ac_cluster_qc_nodes(const ac_cluster_tree* t, const double* asym, uint32_t n, const uint64_t* seq_len, const uint32_t* assembly,
+                        const uint32_t* cluster_weight, const uint8_t* trusted, double cutoff, uint32_t min_assemblies,
+                        const uint16_t* cluster_nodes, uint32_t n_nodes, const uint16_t* manual, uint32_t n_manual, int device, ac_cluster_qc** out) {
+    return guarded([&] {
+        ClusterQcIndex ix;
+        cluster_qc_prologue(t, asym, n, seq_len, assembly, cluster_weight, trusted, cutoff, manual, n_manual, out, &ix);
+        (void)cluster_qc_nodes_checked(ix, cluster_nodes, n_nodes);      // (before a device is selected)
+        auto h = std::make_unique<ac_cluster_qc>();
+        ClusterQcDeviceStats st;
+        if (n_manual) cluster_qc_nodes_host(ix, cluster_nodes, n_nodes, manual, n_manual, min_assemblies, ClusterQcEvaluate(), &h->r);
+        else {
+            DeviceCall call(device);
+            cluster_qc_device(asym, n, ix.dfs_tip.data(), cutoff,
+                              [&](const ClusterQcEvaluate& ev) { cluster_qc_nodes_host(ix, cluster_nodes, n_nodes, nullptr, 0, min_assemblies, ev, &h->r); }, &st);
+        }
+        h->publish(n, false, st);
+        *out = h.release();
+    });
+}
+int ac_cluster_qc_clusters(const ac_cluster_qc* q, const uint16_t** nodes, uint32_t* n_nodes) {
+    return guarded([&] {
+        if (!q || !nodes || !n_nodes) throw DeviceError("null pointer");
+        *nodes = q->r.nodes.data(); *n_nodes = (uint32_t)q->r.nodes.size();
+    });
+}
+int ac_cluster_qc_assignment(const ac_cluster_qc* q, const uint16_t** cluster_of_seq, uint32_t* n) {
+    return guarded([&] {
+        if (!q || !cluster_of_seq || !n) throw DeviceError("null pointer");
+        *cluster_of_seq = q->r.cluster_of_seq.data(); *n = (uint32_t)q->r.cluster_of_seq.size();
+    });
+}
+int ac_cluster_qc_records(const ac_cluster_qc* q, const ac_cluster_qc_record** records, uint32_t* n) {
+    return guarded([&] {
+        if (!q || !records || !n) throw DeviceError("null pointer");
+        *records = q->records.data(); *n = (uint32_t)q->records.size();
+    });
+}
+int ac_cluster_qc_metrics(const ac_cluster_qc* q, ac_clustering_metrics* out) {
+    return guarded([&] {
+        if (!q || !out) throw DeviceError("null pointer");
+        *out = q->metrics;
+    });
+}
+int ac_cluster_qc_trace(const ac_cluster_qc* q, const uint32_t** round_alternatives, uint32_t* n_rounds, const double** scores,
+                        const uint8_t** accepted, uint64_t* n_scores) {
+    return guarded([&] {
+        if (!q || !round_alternatives || !n_rounds || !scores || !accepted || !n_scores) throw DeviceError("null pointer");
+        *round_alternatives = q->r.round_alternatives.data(); *n_rounds = (uint32_t)q->r.round_alternatives.size();
+        *scores = q->r.scores.data(); *accepted = q->r.accepted.data(); *n_scores = q->r.scores.size();
+    });
+}
+size_t ac_cluster_qc_summary_get_sized(const ac_cluster_qc* q, ac_cluster_qc_summary* out, size_t out_size) {
+    if (q && out) memcpy(out, &q->summary, std::min(out_size, sizeof(ac_cluster_qc_summary)));
+    return sizeof(ac_cluster_qc_summary);
+}
+void ac_cluster_qc_free(ac_cluster_qc* q) { delete q; }
+int ac_cluster_min_assemblies(const uint32_t* assembly, uint32_t n, uint32_t* out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer");
+        if (n == 0) throw DeviceError("cluster: no sequences");
+        *out = cluster_min_assemblies(cluster_assembly_count_checked(assembly, n));
+    });
+}
+int ac_cluster_seq_inputs(const ac_graph* g, uint64_t* seq_len, uint32_t* assembly, uint32_t* cluster_weight, uint8_t* trusted, uint32_t* n_assemblies) {
+    return guarded([&] {
+        if (!g) throw DeviceError("null pointer");
+        const size_t n = g->seq_ids.size();
+        if (g->filenames.size() != n || g->headers.size() != n || g->seq_lens.size() != n)
+            throw DeviceError("cluster: this graph carries no file names and headers (load it with ac_graph_from_gfa)");
+        std::vector<uint32_t> number(n);
+        const uint32_t distinct = cluster_number_assemblies(g->filenames, number.data());
+        for (size_t i = 0; i < n; i++) {
+            if (seq_len) seq_len[i] = g->seq_lens[i];
+            if (assembly) assembly[i] = number[i];
+            if (cluster_weight) cluster_weight[i] = cluster_header_weight(g->headers[i]);
+            if (trusted) trusted[i] = cluster_header_trusted(g->headers[i]) ? 1 : 0;
+        }
+        if (n_assemblies) *n_assemblies = distinct;
     });
 }
 

@@ -15,6 +15,7 @@
 #include "trim_host.hpp"
 #include "resolve_host.hpp"
 #include "cluster_host.hpp"
+#include "cluster_qc_host.hpp"
 
 namespace ac {
 
@@ -199,6 +200,16 @@ struct ClusterDeviceStats { double seconds = 0; uint64_t rescans = 0, compares =
 void cluster_merges_device(const double* asym, uint32_t n, std::vector<ClusterRowMerge>* merges, ClusterDeviceStats* st);
 void cluster_merges_graph_device(const FinalGraph& g, uint32_t n_seqs, double* asym_out, std::vector<ClusterRowMerge>* merges, ClusterDeviceStats* st);
 uint32_t cluster_max_seqs();      // most sequences the merge loop takes
+// qc_clusters' matrix work on the device (kernels_cluster_qc.inc): starts an arena session, uploads the n x n matrix, packs the contain bits
+// in the tree's depth-first tip order (dfs_tip: position -> row) and then runs `body`, handing it the function that evaluates one
+// ClusterQcPlan (all alternatives of a refinement round): a fixed number of launches and one read-back each.  cluster_qc_host.cpp drives it.
+struct ClusterQcDeviceStats {
+    double seconds = 0;
+    uint32_t launches = 0, readbacks = 0, evaluations = 0, pair_batches = 0;
+    uint64_t alternatives = 0, pairs_counted = 0, bytes_read_back = 0;
+};
+void cluster_qc_device(const double* asym, uint32_t n, const uint32_t* dfs_tip, double cutoff, const std::function<void(const ClusterQcEvaluate&)>& body,
+                       ClusterQcDeviceStats* st);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

@@ -449,8 +449,9 @@ uint32_t ac_resolve_max_path(void);   /* 65536 entries: the longest path a dista
  * Errors (return 1, ac_last_error), all found before anything is launched except the last: n == 0; ids that do not ascend strictly;
  * largest id + n - 1 > 65535 (the reference's u16 node counter would overflow); n > ac_cluster_max_seqs(); a distance that is NaN,
  * infinite or negative (a device flag, read once after the loop).
- * Not done here (the caller's): refine_auto_clusters / score_clustering / clustering_metrics, the QC verdicts, set_min_assemblies, the
- * per-cluster GFAs, the TSV / YAML / PHYLIP files. */
+ * After the tree: ac_cluster_generate / ac_cluster_qc_nodes below (refine_auto_clusters, score_clustering, clustering_metrics, the QC
+ * verdicts) and ac_cluster_min_assemblies (set_min_assemblies).
+ * Not done here (the caller's): the per-cluster GFAs, the TSV / YAML / PHYLIP files. */
 typedef struct ac_cluster_tree ac_cluster_tree;
 typedef struct {
     uint16_t id;                 /* a tip: the sequence id; an internal node: largest id + 1, + 2, ... in merge order */
@@ -502,6 +503,85 @@ int ac_cluster_containment(const double* asym, uint32_t n, const uint16_t* clust
  * "(...:root_length);" wrapper when the root's distance is below 0.5, and the newline).  Numbers as Rust's `{}` prints an f64.  tip_names:
  * one per tip in tip order (Sequence::string_for_newick), or NULL (the ids).  Free *out with ac_string_free. */
 int ac_cluster_newick(const ac_cluster_tree*, const char* const* tip_names, int file_form, char** out);
+
+/* `autocycler cluster` after the tree: generate_clusters (cluster.rs:497-508) = the cut, refine_auto_clusters (:607-630) when there are no
+ * manual clusters, check_complete_coverage, the final qc_clusters (:511-570) with its pass / fail verdicts, and clustering_metrics (:852-879).
+ * Inputs: the tree; the S x S asymmetric matrix of ac_pairwise_distances / ac_cluster_tree_build (row-major, rows in tip order); and one
+ * entry per tip, in tip order: seq_len, assembly (the index 0 .. F - 1 of the sequence's file name, every index in use), cluster_weight
+ * (Sequence::cluster_weight) and trusted (Sequence::is_trusted).  ac_cluster_seq_inputs fills the four from a graph loaded from a GFA.
+ * Where the work happens.  Whether cluster x is "contained" in cluster y (cluster_is_contained_in_another :692-723: d(a,b) < d(b,a) and
+ * d(a,b) < cutoff for more than half of the sequence pairs) and the order-dependent chain over it (:560-567) run on the device for ALL
+ * alternatives of a refinement round at once: the matrix goes up once per call and becomes one bit per ordered sequence pair; a round then
+ * costs a fixed number of launches and one read-back of one word per cluster and alternative, whatever the number of alternatives.  The
+ * comparison contain / total > 0.5 is made as 2 * contain > total in integers (the same for every total <= 2^28).  Per-node facts, the f64
+ * scores and the accept walk (alt_score > best_score + 1e-12, every alternative of a round computed from the round's start, the LAST one
+ * that beat the running best wins) are the host's.  With manual clusters nothing is launched and the matrix is not read.
+ * Arithmetic of the scores.  The reference sums the balance terms in HashMap order; the library fixes c ascending:
+ *   balance = (sum over c = 1 .. max of ((double)ones_c / (double)F) * (double)size_c) / (double)S,
+ *   tightness = (sum over the passing c ascending of (1.0 - sqrt(dist_c)) * (double)size_c) / (double)(their total size), 0 when none pass,
+ *   overall = (balance + tightness) / 2.0.  Bit for bit the reference's wherever every balance term is exact (e.g. F a power of two).
+ * Where several passing clusters contain c the reference names whichever its HashMap yields first; the library names the smallest number.
+ * Errors (return 1, ac_last_error), found before anything is launched: a tip count that is not n; a node id that is not in the tree; node
+ * lists that do not cover every tip exactly once (the reference panics); nested manual clusters; assembly indices that are not dense.  A
+ * NaN, infinite or negative distance is a device flag that comes back with the first read-back.  min_assemblies == 0 fails nothing. */
+typedef struct ac_cluster_qc ac_cluster_qc;
+typedef struct {
+    uint16_t node;               /* the cluster's node id */
+    uint16_t container;          /* fail & 4: the smallest passing cluster number that contains this one; else 0 */
+    uint32_t size;               /* sequences */
+    uint32_t assembly_count;     /* cluster_assembly_count (:573-585): per file name the largest cluster_weight, summed */
+    uint32_t fail;               /* 0 = passes; 1 = not included in manual clusters, 2 = present in too few assemblies, 4 = contained */
+    uint32_t trusted;
+    uint32_t reserved;
+    uint64_t median_length;      /* median_usize of the sequence lengths: what reorder_clusters sorted by */
+    double cluster_dist;         /* max_pairwise_distance */
+} ac_cluster_qc_record;
+typedef struct {                 /* ClusteringMetrics (metrics.rs:111-121) */
+    uint32_t pass_cluster_count, fail_cluster_count, pass_contig_count, fail_contig_count;
+    double pass_contig_fraction, fail_contig_fraction, cluster_balance_score, cluster_tightness_score, overall_clustering_score;
+} ac_clustering_metrics;
+typedef struct {
+    uint32_t n_seqs, n_clusters;
+    uint32_t rounds;             /* passes of refine_auto_clusters' loop (the last one accepted nothing); 0 for manual clusters and qc_nodes */
+    uint32_t evaluations;        /* clusterings or rounds scored on the device: 1 + the rounds that had an alternative; 0 with manual clusters */
+    uint32_t pair_batches;       /* launches of the pair kernel: one per evaluation unless AC_CLUSTER_QC_PAIR_BATCH cuts them */
+    uint32_t launches;           /* evaluations ? 1 + pair_batches + evaluations : 0 */
+    uint32_t readbacks;          /* == evaluations */
+    uint32_t reserved;
+    uint64_t alternatives;       /* clusterings scored, the start included */
+    uint64_t node_pairs;         /* ordered cluster pairs counted on the device */
+    uint64_t bytes_read_back;
+    double seconds;              /* the evaluations, by device events */
+    double start_score;          /* overall score of the clustering refinement started from */
+} ac_cluster_qc_summary;
+int ac_cluster_generate(const ac_cluster_tree*, const double* asym, uint32_t n, const uint64_t* seq_len, const uint32_t* assembly,
+                        const uint32_t* cluster_weight, const uint8_t* trusted, double cutoff, uint32_t min_assemblies,
+                        const uint16_t* manual, uint32_t n_manual, int device, ac_cluster_qc** out);
+/* qc_clusters alone on the caller's node list (cluster k + 1 = cluster_nodes[k]: the old number reorder_clusters breaks ties by): the final
+ * verdicts without refinement, and the score of one clustering. */
+int ac_cluster_qc_nodes(const ac_cluster_tree*, const double* asym, uint32_t n, const uint64_t* seq_len, const uint32_t* assembly,
+                        const uint32_t* cluster_weight, const uint8_t* trusted, double cutoff, uint32_t min_assemblies,
+                        const uint16_t* cluster_nodes, uint32_t n_nodes, const uint16_t* manual, uint32_t n_manual, int device, ac_cluster_qc** out);
+/* The arrays belong to the handle.  clusters: the node ids of the final clustering (ascending from ac_cluster_generate; as given from
+ * ac_cluster_qc_nodes).  assignment: the reordered cluster number of every tip, in tip order.  records: one per reordered cluster. */
+int ac_cluster_qc_clusters(const ac_cluster_qc*, const uint16_t** nodes, uint32_t* n_nodes);
+int ac_cluster_qc_assignment(const ac_cluster_qc*, const uint16_t** cluster_of_seq, uint32_t* n);
+int ac_cluster_qc_records(const ac_cluster_qc*, const ac_cluster_qc_record** records, uint32_t* n);
+int ac_cluster_qc_metrics(const ac_cluster_qc*, ac_clustering_metrics* out);
+/* The refinement: per round the number of alternatives (split_clusters :311-335, in its order); scores / accepted hold every alternative's
+ * overall score and whether it replaced the running best, round after round (n_scores = the sum of round_alternatives). */
+int ac_cluster_qc_trace(const ac_cluster_qc*, const uint32_t** round_alternatives, uint32_t* n_rounds, const double** scores,
+                        const uint8_t** accepted, uint64_t* n_scores);
+/* at most out_size bytes are written; returns the library's sizeof(ac_cluster_qc_summary) */
+size_t ac_cluster_qc_summary_get_sized(const ac_cluster_qc*, ac_cluster_qc_summary* out, size_t out_size);
+void ac_cluster_qc_free(ac_cluster_qc*);
+/* set_min_assemblies (cluster.rs:645-661) without a user's value: F == 1 -> 1, else max(2, (F + 2) / 4); F = the distinct (dense) indices */
+int ac_cluster_min_assemblies(const uint32_t* assembly, uint32_t n, uint32_t* out);
+/* The four per-sequence arrays (ac_graph_seq_count entries each; any may be NULL) from a handle that carries file names and headers
+ * (ac_graph_from_gfa): assembly numbered by first appearance of the file name; trusted = the lowercased header contains
+ * "autocycler_trusted"; cluster_weight = the first whitespace-separated token of the lowercased header that is
+ * "autocycler_cluster_weight=" followed by an unsigned integer, else 1 (sequence.rs:89-102; values beyond 2^32 - 1 saturate). */
+int ac_cluster_seq_inputs(const ac_graph*, uint64_t* seq_len, uint32_t* assembly, uint32_t* cluster_weight, uint8_t* trusted, uint32_t* n_assemblies);
 
 /* Read-based unitig depths, the --reads step of `autocycler combine` (set_read_depths, depth.rs:45-76; combine.rs:43-46 calls it): a table
  * of the consensus assembly's canonical k-mers (every k-mer of every unitig's forward sequence plus the k-mers that run across a link,
@@ -643,8 +723,11 @@ const char* ac_version(void);
  *      ac_resolve_* accessors with ac_bridge and ac_resolve_summary, ac_resolve_max_path, ac_resolve_free.
  *   9: additions only: ac_cluster_tree_build, ac_cluster_tree_from_distances, ac_cluster_tree_from_nodes, ac_cluster_nodes,
  *      ac_cluster_merges, ac_cluster_summary_get_sized, ac_cluster_cut, ac_cluster_assign, ac_cluster_containment, ac_cluster_newick,
- *      ac_cluster_max_seqs, ac_cluster_free with ac_cluster_node, ac_cluster_merge and ac_cluster_summary. */
-#define AC_ABI_VERSION 9
+ *      ac_cluster_max_seqs, ac_cluster_free with ac_cluster_node, ac_cluster_merge and ac_cluster_summary.
+ *  10: additions only: ac_cluster_generate, ac_cluster_qc_nodes, ac_cluster_qc_clusters, ac_cluster_qc_assignment, ac_cluster_qc_records,
+ *      ac_cluster_qc_metrics, ac_cluster_qc_trace, ac_cluster_qc_summary_get_sized, ac_cluster_qc_free, ac_cluster_min_assemblies,
+ *      ac_cluster_seq_inputs with ac_cluster_qc_record, ac_clustering_metrics and ac_cluster_qc_summary. */
+#define AC_ABI_VERSION 10
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
