@@ -154,7 +154,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -289,6 +289,15 @@ def load_library(path=None):
     lib.ac_selftest_sort_cmp.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ac_selftest_scan_pool.argtypes = [C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.ac_selftest_wave.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_fills.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.ac_selftest_fill_order.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
+    lib.ac_selftest_readback.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_scalar_chain.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_arena.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_launch.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_atomics.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ac_selftest_side_order.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_void_p]
+    lib.ac_selftest_event_ring.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
     _libs[key] = lib
     return lib
 
@@ -1026,6 +1035,126 @@ def selftest_wave(program, in_u64, aux_i32, live_mask, out_init, device=0, lib_p
     assert i.size == 256 and a.size == 256 and m.size == 4 and out.size == 256
     _check(lib, lib.ac_selftest_wave(device, program, i.ctypes.data, a.ctypes.data, m.ctypes.data, out.ctypes.data))
     return out
+
+
+# ---- test hooks: one facility of the device runtime on numpy arrays (csrc/selftest_runtime.inc; tests/runtime_cases.py holds the references) ----
+FILL_KINDS = {"all": 0, "from": 1, "first": 2, "side_stream": 3}
+FILL_TRIGGERS = {"none": 0, "launch": 1, "launch_full": 2, "launch_wave_kernel": 3, "copy_h2d": 4, "copy_d2h": 5, "copy_d2d": 6, "stream_sync": 7,
+                 "arena_rewind": 8, "after_main": 9, "main_event": 10}
+READ_PATHS = {"copy_d2h": 0, "batch": 1, "batch_twice": 2, "to_host": 3, "read_scalar": 4, "side_stream": 5}
+ARENA_OPS = {"alloc": 0, "mark": 1, "rewind": 2, "reset": 3, "reserve": 4, "release_all": 5, "set_grow": 6}
+LAUNCHERS = {"launch": 0, "launch_full": 1, "launch_wave_kernel": 2, "sized": 3}
+ATOMIC_OPS = {"add32": 0, "add64": 1, "min32": 2, "max32": 3, "min64": 4, "max64": 5, "or32": 6, "or64": 7, "xor64": 8, "fetch_or32": 9, "fetch_and32": 10,
+              "cas32": 11, "cas64": 12, "load32": 13, "wave_alloc32": 14, "wave_add64": 15}
+ATOMIC_THREADS = 64 * 256
+LAUNCH_SLOTS = 1024
+
+
+def selftest_fills(regions, trigger, pattern, drop_on_reset=False, device=0, lib_path=None):
+    """ac_selftest_fills: regions = [(bytes, kind, arg, byte)], pattern = the whole span's bytes -> (the span afterwards, (launches while queueing,
+    launches up to and including the trigger))."""
+    import numpy as np
+    lib = load_library(lib_path)
+    r = _np_in([(b, FILL_KINDS[k], a, v) for b, k, a, v in regions], np.uint64)
+    span = np.array(pattern, dtype=np.uint8)
+    launches = np.zeros(2, dtype=np.uint32)
+    _check(lib, lib.ac_selftest_fills(device, r.ctypes.data, len(regions), FILL_TRIGGERS[trigger], int(drop_on_reset), span.ctypes.data, span.size, launches.ctypes.data))
+    return span, (int(launches[0]), int(launches[1]))
+
+
+def selftest_fill_order(n, byte1, w_lo, w_hi, w_val, from2, byte2, upto3, byte3, device=0, lib_path=None):
+    """ac_selftest_fill_order -> the n bytes after fill, functor store, fill_bytes_from and fill_bytes_first."""
+    import numpy as np
+    lib = load_library(lib_path)
+    out = np.empty(n, dtype=np.uint8)
+    _check(lib, lib.ac_selftest_fill_order(device, n, byte1, w_lo, w_hi, w_val, from2, byte2, upto3, byte3, out.ctypes.data))
+    return out
+
+
+def selftest_readback(data, path, items, device=0, lib_path=None):
+    """ac_selftest_readback: items = [(offset, bytes)] -> ([the bytes each item brought back], launches, read-backs)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    d = _np_in(data, np.uint8)
+    it = _np_in(items, np.uint64).reshape(-1, 2)
+    out = np.full(int(it[:, 1].sum()) + 1, 0xA5, dtype=np.uint8)
+    counters = np.zeros(2, dtype=np.uint32)
+    _check(lib, lib.ac_selftest_readback(device, d.ctypes.data, d.size, READ_PATHS[path], it.ctypes.data, it.shape[0], out.ctypes.data, counters.ctypes.data))
+    assert out[-1] == 0xA5      # nothing was written behind the last item
+    ends = np.cumsum(it[:, 1]).astype(np.int64)
+    return [out[e - int(b):e] for e, b in zip(ends, it[:, 1])], int(counters[0]), int(counters[1])
+
+
+def selftest_scalar_chain(values, device=0, lib_path=None):
+    """ac_selftest_scalar_chain -> (what each read_scalar saw, launches, read-backs)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    v = _np_in(values, np.uint64)
+    out = np.zeros_like(v)
+    counters = np.zeros(2, dtype=np.uint32)
+    _check(lib, lib.ac_selftest_scalar_chain(device, v.ctypes.data, v.size, out.ctypes.data, counters.ctypes.data))
+    return out, int(counters[0]), int(counters[1])
+
+
+def selftest_arena(ops, live, device=0, lib_path=None):
+    """ac_selftest_arena: ops = [(name of ARENA_OPS, arg)], live[ordinal] = read that allocation back at the end -> (totals[n_ops, 3],
+    placements[n_allocs, 3], wrong[n_allocs]: bytes that do not hold the ordinal, -1 where not read)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    o = _np_in([(ARENA_OPS[c], a) for c, a in ops], np.uint64).reshape(-1, 2)
+    n_allocs = int((o[:, 0] == 0).sum())
+    lv = _np_in(live, np.uint8)
+    assert lv.size == n_allocs
+    totals = np.zeros((len(ops), 3), dtype=np.uint64)
+    allocs = np.zeros((max(n_allocs, 1), 3), dtype=np.uint64)
+    wrong = np.full(max(n_allocs, 1), np.iinfo(np.uint64).max, dtype=np.uint64)
+    lvp = np.zeros(max(n_allocs, 1), dtype=np.uint8); lvp[:n_allocs] = lv
+    _check(lib, lib.ac_selftest_arena(device, o.ctypes.data, len(ops), totals.ctypes.data, allocs.ctypes.data, lvp.ctypes.data, wrong.ctypes.data))
+    return totals, allocs[:n_allocs], wrong[:n_allocs].astype(np.int64)
+
+
+def selftest_launch(which, n, device=0, lib_path=None):
+    """ac_selftest_launch -> (slots[1024, 4] = {threads, sum, xor, lanes beyond n}, "grid too large" was thrown, launches)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    slots = np.zeros((LAUNCH_SLOTS, 4), dtype=np.uint64)
+    info = np.zeros(2, dtype=np.uint32)
+    _check(lib, lib.ac_selftest_launch(device, LAUNCHERS[which], n, slots.ctypes.data, info.ctypes.data))
+    return slots, bool(info[0]), int(info[1])
+
+
+def selftest_atomics(op, init, operand, target, n_words, expected=0, device=0, lib_path=None):
+    """ac_selftest_atomics -> (the words afterwards, what each of the 16384 threads' calls returned)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    v, t = _np_in(operand, np.uint64), _np_in(target, np.uint32)
+    assert v.size == ATOMIC_THREADS and t.size == ATOMIC_THREADS
+    words = np.zeros(n_words, dtype=np.uint64); ret = np.zeros(ATOMIC_THREADS, dtype=np.uint64)
+    _check(lib, lib.ac_selftest_atomics(device, ATOMIC_OPS[op], init, expected, v.ctypes.data, t.ctypes.data, n_words, words.ctypes.data, ret.ctypes.data))
+    return words, ret
+
+
+def selftest_side_order(mode, which, seed, n_words, device=0, lib_path=None):
+    """ac_selftest_side_order: mode "after_main" or "main_event" -> the words the host saw."""
+    import numpy as np
+    lib = load_library(lib_path)
+    out = np.zeros(n_words, dtype=np.uint32)
+    _check(lib, lib.ac_selftest_side_order(device, {"after_main": 0, "main_event": 1}[mode], which, seed, n_words, out.ctypes.data))
+    return out
+
+
+def selftest_event_ring(kinds=None, device=0, lib_path=None):
+    """ac_selftest_event_ring.  kinds None: read and clear; else kinds[0] = how the handle is taken ("main_event" / "mark"), kinds[1:] = the
+    events taken before it is waited for (those or "after_main") -> dict(events_taken, recycled_waits)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    out = np.zeros(2, dtype=np.uint64)
+    if kinds is None:
+        _check(lib, lib.ac_selftest_event_ring(device, 0, None, 0, out.ctypes.data))
+    else:
+        k = _np_in([{"main_event": 0, "mark": 1, "after_main": 2}[x] for x in kinds], np.uint8)
+        _check(lib, lib.ac_selftest_event_ring(device, 1, k.ctypes.data, k.size - 1, out.ctypes.data))
+    return dict(events_taken=int(out[0]), recycled_waits=int(out[1]))
 
 
 class VerifyReport(C.Structure):

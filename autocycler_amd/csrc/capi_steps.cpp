@@ -723,6 +723,35 @@ int ac_selftest_scan_pool(int device, int op, uint64_t value, uint64_t* out) {
 int ac_selftest_wave(int device, int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64) {
     return guarded([&] { DeviceCall call(device); selftest_wave(program, in_u64, aux_i32, live_mask, out_u64); });
 }
+// One facility of the device runtime on the caller's data — test hooks (selftest_runtime.inc).
+int ac_selftest_fills(int device, const uint64_t* regions, uint64_t n_regions, int trigger, int mode, uint8_t* span, uint64_t span_bytes, uint32_t* launches_out) {
+    return guarded([&] { DeviceCall call(device); selftest_fills(regions, n_regions, trigger, mode, span, span_bytes, launches_out); });
+}
+int ac_selftest_fill_order(int device, uint64_t n, int byte1, uint64_t w_lo, uint64_t w_hi, int w_val, uint64_t from2, int byte2, uint64_t upto3, int byte3, uint8_t* out) {
+    return guarded([&] { DeviceCall call(device); selftest_fill_order(n, byte1, w_lo, w_hi, w_val, from2, byte2, upto3, byte3, out); });
+}
+int ac_selftest_readback(int device, const uint8_t* data, uint64_t n_data, int path, const uint64_t* items, uint64_t n_items, uint8_t* out, uint32_t* counters_out) {
+    return guarded([&] { DeviceCall call(device); selftest_readback(data, n_data, path, items, n_items, out, counters_out); });
+}
+int ac_selftest_scalar_chain(int device, const uint64_t* values, uint64_t n, uint64_t* out, uint32_t* counters_out) {
+    return guarded([&] { DeviceCall call(device); selftest_scalar_chain(values, n, out, counters_out); });
+}
+int ac_selftest_arena(int device, const uint64_t* ops, uint64_t n_ops, uint64_t* totals_out, uint64_t* allocs_out, const uint8_t* live, uint64_t* wrong_out) {
+    return guarded([&] { DeviceCall call(device); selftest_arena(ops, n_ops, totals_out, allocs_out, live, wrong_out); });
+}
+int ac_selftest_launch(int device, int which, uint64_t n, uint64_t* slots_out, uint32_t* info_out) {
+    return guarded([&] { DeviceCall call(device); selftest_launch(which, n, slots_out, info_out); });
+}
+int ac_selftest_atomics(int device, int op, uint64_t init, uint64_t expected, const uint64_t* operand, const uint32_t* target, uint32_t n_words, uint64_t* words_out,
+                        uint64_t* returns_out) {
+    return guarded([&] { DeviceCall call(device); selftest_atomics(op, init, expected, operand, target, n_words, words_out, returns_out); });
+}
+int ac_selftest_side_order(int device, int mode, int which, uint32_t seed, uint64_t n_words, uint32_t* out_words) {
+    return guarded([&] { DeviceCall call(device); selftest_side_order(mode, which, seed, n_words, out_words); });
+}
+int ac_selftest_event_ring(int device, int op, const uint8_t* kinds, uint32_t n_more, uint64_t* out) {
+    return guarded([&] { DeviceCall call(device); selftest_event_ring(op, kinds, n_more, out); });
+}
 
 int ac_random_access_ceilings_at(int device, uint64_t table_slots, double* cas_gops, double* read_gops) {
     return guarded([&] {

@@ -186,6 +186,17 @@ class Arena {
     size_t total_used() const { size_t t = 0; for (auto& b : blocks_) t += b.used; return t; }
     size_t capacity() const { size_t t = 0; for (auto& b : blocks_) t += b.cap; return t; }
     void set_grow(size_t g) { grow_ = g; }
+    size_t grow() const { return grow_; }
+    // Which block an address lies in, where, and how much of that block is handed out (tests: selftest_runtime.inc); false: in none.
+    bool locate(const void* p, size_t* block, size_t* offset, size_t* used) const {
+        for (size_t i = 0; i < blocks_.size(); i++) {
+            const char* lo = (const char*)blocks_[i].p;
+            if ((const char*)p < lo || (const char*)p >= lo + blocks_[i].cap) continue;
+            *block = i; *offset = (size_t)((const char*)p - lo); *used = blocks_[i].used;
+            return true;
+        }
+        return false;
+    }
 
   private:
     struct Block { void* p; size_t cap, used; };
@@ -550,6 +561,7 @@ inline void copy_d2h(void* h, const void* d, size_t bytes, stream_t s = 0) {
 #endif
     copy_d2h_async(h, d, bytes, s);
 #ifndef AC_EMU
+    rt_counters().readbacks++;      // (a host round trip like the two above)
     AC_HIP_CHECK(hipStreamSynchronize(s));
 #endif
 }
@@ -651,12 +663,12 @@ class SideStream {
     void after_main(int which = 0) {
 #ifndef AC_EMU
         stream_t s = stream(which);
-        hipEvent_t e = ev_[next_++ % N_EV];
+        hipEvent_t e = ev_[take(false)];
         flush_fills();
         AC_HIP_CHECK(hipEventRecord(e, 0));
         AC_HIP_CHECK(hipStreamWaitEvent(s, e, 0));
 #else
-        (void)which;
+        (void)which; (void)take(false);
 #endif
     }
     // An event that fires when everything enqueued on STREAM 0 so far is done, and the host's wait for it (a poll: the caller is about to issue
@@ -664,15 +676,16 @@ class SideStream {
     void* main_event() {
 #ifndef AC_EMU
         (void)stream();
-        hipEvent_t e = ev_[next_++ % N_EV];
+        hipEvent_t e = ev_[take(true)];
         flush_fills();
         AC_HIP_CHECK(hipEventRecord(e, 0));
         return (void*)e;
 #else
-        return nullptr;
+        return (void*)&ev_[take(true)];
 #endif
     }
     static void wait_event(void* ev) {
+        get().consumed(ev);
 #ifndef AC_EMU
         for (;;) {
             const hipError_t e = hipEventQuery((hipEvent_t)ev);
@@ -682,19 +695,18 @@ class SideStream {
             for (int i = 0; i < 32; i++) __builtin_ia32_pause();
 #endif
         }
-#else
-        (void)ev;
 #endif
     }
-    // An event that fires when everything enqueued on the side stream so far is done (valid until N_EV more events were taken).
-    void* mark() {
+    // An event that fires when everything enqueued on the side stream `which` so far is done (valid until N_EV more events were taken).
+    void* mark(int which = 0) {
 #ifndef AC_EMU
-        stream_t s = stream();
-        hipEvent_t e = ev_[next_++ % N_EV];
+        stream_t s = stream(which);
+        hipEvent_t e = ev_[take(true)];
         AC_HIP_CHECK(hipEventRecord(e, s));
         return (void*)e;
 #else
-        return nullptr;
+        (void)which;
+        return (void*)&ev_[take(true)];
 #endif
     }
     void sync() noexcept {
@@ -704,7 +716,41 @@ class SideStream {
     }
     struct Guard { ~Guard() { SideStream::get().sync(); } };   // no copy may outlive the scope that owns its destination
 
+    // ---- the ring's bookkeeping (host integers only; a worker thread may consume a handle: one mutex) ----
+    // Whoever waits for a handle of main_event() / mark() by other means than wait_event() says so here.  The slot is found by the handle (N_EV
+    // compares); a handle whose slot has gone out again since it was handed out names the NEWER recording: counted in recycled_waits.
+    void consumed(void* ev) {
+        std::lock_guard<std::mutex> lock(mu_);
+        for (unsigned i = 0; i < N_EV && ev; i++) {
+#ifndef AC_EMU
+            if ((void*)ev_[i] != ev) continue;
+#else
+            if ((void*)&ev_[i] != ev) continue;
+#endif
+            if (held_[i] && held_[i] != issue_[i]) recycled_waits_++;
+            held_[i] = 0;
+            return;
+        }
+    }
+    struct RingCounts { u64 events_taken, recycled_waits; };
+    // Reads and clears both counts; handles still outstanding are forgotten (the caller starts a new accounting period).
+    RingCounts take_ring_counts() {
+        std::lock_guard<std::mutex> lock(mu_);
+        const RingCounts c{events_taken_, recycled_waits_};
+        events_taken_ = 0; recycled_waits_ = 0;
+        for (auto& h : held_) h = 0;
+        return c;
+    }
+
   private:
+    unsigned take(bool as_handle) {      // the next slot of the ring; its issue number; as_handle: the caller keeps the event
+        std::lock_guard<std::mutex> lock(mu_);
+        const unsigned slot = next_++ % N_EV;
+        issue_[slot] = ++issued_;
+        events_taken_++;
+        if (as_handle && !held_[slot]) held_[slot] = issue_[slot];      // (an older handle nobody consumed yet stays the one on record)
+        return slot;
+    }
     void destroy() {
 #ifndef AC_EMU
         if (created_) { (void)hipStreamDestroy(s_); (void)hipStreamDestroy(s2_); for (auto& e : ev_) (void)hipEventDestroy(e); created_ = false; }
@@ -712,8 +758,14 @@ class SideStream {
     }
 #ifndef AC_EMU
     hipStream_t s_ = nullptr, s2_ = nullptr;
-    hipEvent_t ev_[64];
+    hipEvent_t ev_[N_EV] = {};
+#else
+    char ev_[N_EV] = {};      // (a handle is the address of its slot)
 #endif
+    std::mutex mu_;
+    u64 issue_[N_EV] = {};      // per slot: the number of its latest hand-out (1, 2, ...; 0: never)
+    u64 held_[N_EV] = {};       // per slot: the issue number under which it went out as a handle that nobody has consumed yet (0: none)
+    u64 issued_ = 0, events_taken_ = 0, recycled_waits_ = 0;
     bool created_ = false;
     int dev_ = -1;
     unsigned next_ = 0;

@@ -254,5 +254,6 @@ void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind) {
 }
 
 #include "selftest_prims.inc"      // the data-in / data-out hooks: one primitive on the caller's arrays (ac_selftest_scan, ...)
+#include "selftest_runtime.inc"    // ... and one facility of the runtime itself (ac_selftest_fills, ...)
 
 }  // namespace ac

@@ -220,6 +220,16 @@ void selftest_segments(int op, const uint32_t* seg, const uint64_t* vals, uint64
 void selftest_sort_cmp(int form, const uint64_t* a, const uint32_t* b, const uint32_t* vals, uint64_t n, uint64_t* a_out, uint32_t* b_out, uint32_t* vals_out);
 void selftest_scan_pool(int op, uint64_t value, uint64_t* out);
 void selftest_wave(int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64);
+// One facility of the device runtime (device_rt.hpp) on the caller's data (tests: the reference is the test's own): selftest_runtime.inc.
+void selftest_fills(const uint64_t* regions, uint64_t n_regions, int trigger, int mode, uint8_t* span, uint64_t span_bytes, uint32_t* launches_out);
+void selftest_fill_order(uint64_t n, int byte1, uint64_t w_lo, uint64_t w_hi, int w_val, uint64_t from2, int byte2, uint64_t upto3, int byte3, uint8_t* out);
+void selftest_readback(const uint8_t* data, uint64_t n_data, int path, const uint64_t* items, uint64_t n_items, uint8_t* out, uint32_t* counters_out);
+void selftest_scalar_chain(const uint64_t* values, uint64_t n, uint64_t* out, uint32_t* counters_out);
+void selftest_arena(const uint64_t* ops, uint64_t n_ops, uint64_t* totals_out, uint64_t* allocs_out, const uint8_t* live, uint64_t* wrong_out);
+void selftest_launch(int which, uint64_t n, uint64_t* slots_out, uint32_t* info_out);
+void selftest_atomics(int op, uint64_t init, uint64_t expected, const uint64_t* operand, const uint32_t* target, uint32_t n_words, uint64_t* words_out, uint64_t* returns_out);
+void selftest_side_order(int mode, int which, uint32_t seed, uint64_t n_words, uint32_t* out_words);
+void selftest_event_ring(int op, const uint8_t* kinds, uint32_t n_more, uint64_t* out);
 
 // Measured ceilings of the device for random atomicCAS / random 8-byte reads on a 134 MB table, in 10^9 operations per second.
 void random_access_ceilings(double* cas_gops, double* read_gops, uint64_t table_slots = (uint64_t)1 << 24);

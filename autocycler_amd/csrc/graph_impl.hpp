@@ -306,7 +306,7 @@ struct PathRemapJob {
     const int32_t* rec_val = nullptr; const u32* rec_pos = nullptr; u64 n_rec = 0;
     const u32* number = nullptr; u32 n_unitigs = 0;      // pinned: final number of seed index r at [r]
     u64 ent_limit = ~0ULL;                               // stretch mode: stretches that begin at or behind this entry are not the host's (the device renumbers that share and sends it over)
-    void* landed = nullptr;                              // event: entries and number table are in host memory
+    void* landed = nullptr; SideStream* side = nullptr;  // event: entries and number table are in host memory (side: the ring it came from)
     int dev = 0;
     std::atomic<u64> next{0}; std::atomic<int> ready{0};      // ready: 0 nobody waits yet, 1 one thread waits for `landed`, 2 go, 3 failed
     std::atomic<u32> bad{0};                             // entries that name no unitig (never, short of a bug: reported as an internal error)
@@ -324,7 +324,7 @@ void path_remap_finish(PathRemapJob& j) noexcept;         // until every thread 
 // result block out while the unitig records and the links are still crossing.
 struct SeqExpandJob {
     const u64* words = nullptr; u8* out = nullptr; u64 total = 0;      // pinned: the codes as they land; the result block (total bytes)
-    void* landed = nullptr; int dev = 0;                                // event: the codes are in host memory
+    void* landed = nullptr; SideStream* side = nullptr; int dev = 0;    // event: the codes are in host memory (side: the ring it came from)
     std::atomic<u64> next{0}; std::atomic<int> ready{0};
     u64 ticket = 0; bool started = false;
     std::atomic<double> t_start{0}, t_ready{0}, t_last{0};      // diagnostics (AC_DEBUG_ARENA): job started / its codes had landed / its last block was done

@@ -83,6 +83,7 @@ void GraphBuilder::Impl::insert(const PackedText& pt, u32 hint, DBuf<u64>* slots
 #ifndef AC_EMU
             if (upload_pending && &pt == &loc && pe + (u64)k + 8192 > upload_avail) {      // this phase reads beyond the first uploaded chunk
                 flush_fills();
+                SideStream::get().consumed(upload_done);
                 AC_HIP_CHECK(hipStreamWaitEvent(0, (hipEvent_t)upload_done, 0));
                 upload_pending = false;
             }

@@ -479,7 +479,7 @@ struct TailRun {
             side.after_main();
             copy_d2h_async(seq_words_block.p, seq_words.ptr(), nw * 8, side.stream());
             seq_job.words = (const u64*)seq_words_block.p; seq_job.out = (u8*)out->seq_block.p; seq_job.total = final_total;
-            seq_job.landed = side.mark();
+            seq_job.landed = side.mark(); seq_job.side = &side;
 #ifndef AC_EMU
             AC_HIP_CHECK(hipGetDevice(&seq_job.dev));
             seq_expand_start(seq_job, 12);
@@ -521,7 +521,7 @@ struct TailRun {
             const int remap_threads = (int)(host_stretch ? 2 * upload_threads() : upload_threads());      // (writing the stretches out is bound by the host's memory, not by its cores' arithmetic: twice the packing threads — configs[4] writes 4.8 GB)
             late_copy([this, U, d_number_only, remap_threads]() {
                 copy_d2h_async(number_block.p, d_number_only, (size_t)U * 4, side.stream());
-                remap_job.landed = side.mark();
+                remap_job.landed = side.mark(); remap_job.side = &side;
 #ifndef AC_EMU
                 AC_HIP_CHECK(hipGetDevice(&remap_job.dev));
                 path_remap_start(remap_job, remap_threads);

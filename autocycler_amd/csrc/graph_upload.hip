@@ -277,6 +277,7 @@ void seq_expand_start(SeqExpandJob& j, int threads) {
     j.ticket = UploadPool::second().start(T, [job, BLOCK] {
         int expect = 0;
         if (job->ready.compare_exchange_strong(expect, 1)) {      // one thread waits for the copy, the others watch it
+            if (job->side) job->side->consumed(job->landed);
             const bool ok = hipSetDevice(job->dev) == hipSuccess && hipEventSynchronize((hipEvent_t)job->landed) == hipSuccess;
             job->t_ready.store(now_s());
             job->ready.store(ok ? 2 : 3, std::memory_order_release);
@@ -321,6 +322,7 @@ void path_remap_start(PathRemapJob& j, int threads) {
     j.ticket = UploadPool::get().start(T, [job, BLOCK] {
         int expect = 0;
         if (job->ready.compare_exchange_strong(expect, 1)) {      // one thread waits for the copies, the others watch it
+            if (job->side) job->side->consumed(job->landed);
             const bool ok = hipSetDevice(job->dev) == hipSuccess && hipEventSynchronize((hipEvent_t)job->landed) == hipSuccess;
             job->t_ready.store(now_s());
             job->ready.store(ok ? 2 : 3, std::memory_order_release);

@@ -200,6 +200,51 @@ int ac_selftest_sort_cmp(int device, int form, const uint64_t* key_a, const uint
 int ac_selftest_scan_pool(int device, int op, uint64_t value, uint64_t* out);
 int ac_selftest_wave(int device, int program, const uint64_t* in_u64, const int32_t* aux_i32, const uint64_t* live_mask, uint64_t* out_u64);
 
+/* Test hooks of the device runtime itself (csrc/device_rt.hpp), data in / data out as above: ONE facility on the caller's host arrays, the
+ * reference is the caller's (tests/runtime_cases.py).  Additive (ABI 11).  Every bad argument is an error return before anything is launched.
+ *   ac_selftest_fills        regions: n_regions x {bytes, kind, arg, byte}; kind 0 fill_bytes, 1 fill_bytes_from(arg), 2 fill_bytes_first(arg), 3
+ *                            fill_bytes on a stream other than 0.  One arena run holds {256-byte sentinel, region rounded up to 256 (an empty one:
+ *                            256)} per region and a last sentinel: span_bytes.  span: in = the pattern uploaded over all of it, out = all of it
+ *                            afterwards.  trigger, what makes the queued fills go out: 0 nothing but the queue filling up (and the final read),
+ *                            1 launch, 2 launch_full, 3 launch_wave_kernel, 4 copy_h2d, 5 copy_d2h, 6 copy_d2d, 7 stream_sync, 8 Arena::rewind, 9
+ *                            SideStream::after_main, 10 SideStream::main_event.  mode 1: the fills are queued, then the arena is reset, the same
+ *                            buffers allocated again and the pattern uploaded: it must come back intact.  launches_out[2] = kernel launches
+ *                            counted {while queueing, up to and including the trigger}.
+ *   ac_selftest_fill_order   fill(byte1) of n bytes, a functor that writes w_val over [w_lo, w_hi), fill_bytes_from(from2, byte2),
+ *                            fill_bytes_first(upto3, byte3) -> out[n].
+ *   ac_selftest_readback     uploads data[n_data], fetches items (n_items x {offset, bytes}) and writes them to out one behind the other.  path 0
+ *                            copy_d2h per item, 1 one ReadBatch, 2 one ReadBatch object run twice (half the items each), 3 to_host, 4
+ *                            read_scalar (4 or 8 aligned bytes), 5 copy_d2h on the side stream behind after_main.  counters_out[2] = {kernel
+ *                            launches, read-backs} of the fetches.
+ *   ac_selftest_scalar_chain n times: a functor stores values[i] into one device word, read_scalar fetches it -> out[i]; counters_out as above.
+ *   ac_selftest_arena        ops: n_ops x {code, arg} on an arena that starts empty; 0 alloc(arg), 1 mark, 2 rewind(mark number arg), 3 reset, 4
+ *                            reserve(arg), 5 release_all, 6 set_grow(arg).  totals_out: n_ops x {capacity, total_used, peak}; allocs_out: per alloc
+ *                            {block ordinal, offset, address}.  Each allocation is filled with its ordinal's low byte on the device; at the end
+ *                            those with live[ordinal] != 0 are read: wrong_out[ordinal] = bytes that hold something else.  The arena is left empty
+ *                            with its own growth step.
+ *   ac_selftest_launch       which 0 launch, 1 launch_full, 2 launch_wave_kernel over n logical threads: slots_out[1024 x 4] = per (workgroup
+ *                            mod 1024) {threads, sum of their indices mod 2^64, xor of their indices, lanes beyond n}.  which 3:
+ *                            launch_wave_kernel_sized with n blocks (0 or more than 2^24 - 1).  info_out[2] = {"grid too large" was thrown, launches}.
+ *   ac_selftest_atomics      64 workgroups x 256 threads; thread t applies op to word target[t] (< n_words; all words start as init) with
+ *                            operand[t].  op 0 add32, 1 add64, 2 min32, 3 max32, 4 min64, 5 max64, 6 or32, 7 or64, 8 xor64, 9 fetch_or32, 10
+ *                            fetch_and32, 11 cas32, 12 cas64 (both compare with `expected`), 13 atomic_load32 of words an earlier launch set to
+ *                            w * 2654435761 + init, 14 wave_alloc32, 15 wave_add64 (one counter per wavefront).  words_out[n_words], returns_out[16384].
+ *   ac_selftest_side_order   a functor on stream 0 writes n_words words (i * 2654435761 + seed); mode 0: after_main(which), a copy on side
+ *                            stream `which`, mark(which), wait_event; mode 1: main_event, wait_event, then the same copy -> out_words.
+ *   ac_selftest_event_ring   op 0: reads and clears {events taken from the side stream's ring, waits on a handle whose slot had gone out again}
+ *                            -> out[2].  op 1: clears, takes a handle (kinds[0]: 0 main_event, 1 mark), n_more further events (kinds[1 ..]: 0, 1,
+ *                            2 after_main), waits for the handle, then as op 0. */
+int ac_selftest_fills(int device, const uint64_t* regions, uint64_t n_regions, int trigger, int mode, uint8_t* span, uint64_t span_bytes, uint32_t* launches_out);
+int ac_selftest_fill_order(int device, uint64_t n, int byte1, uint64_t w_lo, uint64_t w_hi, int w_val, uint64_t from2, int byte2, uint64_t upto3, int byte3, uint8_t* out);
+int ac_selftest_readback(int device, const uint8_t* data, uint64_t n_data, int path, const uint64_t* items, uint64_t n_items, uint8_t* out, uint32_t* counters_out);
+int ac_selftest_scalar_chain(int device, const uint64_t* values, uint64_t n, uint64_t* out, uint32_t* counters_out);
+int ac_selftest_arena(int device, const uint64_t* ops, uint64_t n_ops, uint64_t* totals_out, uint64_t* allocs_out, const uint8_t* live, uint64_t* wrong_out);
+int ac_selftest_launch(int device, int which, uint64_t n, uint64_t* slots_out, uint32_t* info_out);
+int ac_selftest_atomics(int device, int op, uint64_t init, uint64_t expected, const uint64_t* operand, const uint32_t* target, uint32_t n_words, uint64_t* words_out,
+                        uint64_t* returns_out);
+int ac_selftest_side_order(int device, int mode, int which, uint32_t seed, uint64_t n_words, uint32_t* out_words);
+int ac_selftest_event_ring(int device, int op, const uint8_t* kinds, uint32_t n_more, uint64_t* out);
+
 /* The 2-bit packing the host entry applies before the upload (sequence.rs:39-48 validates the same alphabet): n_text bytes ->
  * (n_text + 31) / 32 words of 2-bit codes (A, C, G, T = 0..3, first base most significant) and as many 32-bit mask words
  * (bit i = byte i is not a base).  force_scalar != 0 selects the portable loop instead of the AVX2 / BMI2 one (both are
@@ -726,8 +771,10 @@ const char* ac_version(void);
  *      ac_cluster_max_seqs, ac_cluster_free with ac_cluster_node, ac_cluster_merge and ac_cluster_summary.
  *  10: additions only: ac_cluster_generate, ac_cluster_qc_nodes, ac_cluster_qc_clusters, ac_cluster_qc_assignment, ac_cluster_qc_records,
  *      ac_cluster_qc_metrics, ac_cluster_qc_trace, ac_cluster_qc_summary_get_sized, ac_cluster_qc_free, ac_cluster_min_assemblies,
- *      ac_cluster_seq_inputs with ac_cluster_qc_record, ac_clustering_metrics and ac_cluster_qc_summary. */
-#define AC_ABI_VERSION 10
+ *      ac_cluster_seq_inputs with ac_cluster_qc_record, ac_clustering_metrics and ac_cluster_qc_summary.
+ *  11: additions only: the runtime's test hooks ac_selftest_fills, ac_selftest_fill_order, ac_selftest_readback, ac_selftest_scalar_chain,
+ *      ac_selftest_arena, ac_selftest_launch, ac_selftest_atomics, ac_selftest_side_order, ac_selftest_event_ring. */
+#define AC_ABI_VERSION 11
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
