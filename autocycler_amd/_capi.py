@@ -96,6 +96,20 @@ class ResolveSummary(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("size", "reserved")}
 
 
+class Component(C.Structure):      # ac_component
+    _fields_ = [("first", C.c_uint32), ("unitigs", C.c_uint32), ("length", C.c_uint64), ("links_all", C.c_uint64), ("links_one_way", C.c_uint64),
+                ("open_ends", C.c_uint32), ("marked", C.c_uint32), ("circular_loop", C.c_uint8)]
+
+
+class ComponentsSummary(C.Structure):      # ac_components_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "unitigs", "components", "topology")] + \
+               [(n, C.c_uint64) for n in ("links_all", "links_one_way", "total_length")] + \
+               [("launches", C.c_uint32), ("read_backs", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -154,7 +168,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -244,6 +258,18 @@ def load_library(path=None):
     lib.ac_resolve_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ResolveSummary), C.c_size_t]
     lib.ac_resolve_free.argtypes = [C.c_void_p]
     lib.ac_resolve_free.restype = None
+    lib.ac_graph_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_components_from_links.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_components_records.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Component)), C.POINTER(C.c_uint32)]
+    lib.ac_components_of_unitig.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32))]
+    lib.ac_components_members.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32))]
+    lib.ac_components_unitig_flags.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8))]
+    lib.ac_components_summary_get_sized.restype = C.c_size_t
+    lib.ac_components_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(ComponentsSummary), C.c_size_t]
+    lib.ac_topology_name.restype = C.c_char_p
+    lib.ac_topology_name.argtypes = [C.c_uint32]
+    lib.ac_components_free.argtypes = [C.c_void_p]
+    lib.ac_components_free.restype = None
     lib.ac_cluster_max_seqs.restype = C.c_uint32
     lib.ac_cluster_max_seqs.argtypes = []
     lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -634,6 +660,98 @@ def resolve_bridge_paths(paths, weights, consensus_weights=None, device=0, lib_p
     h = C.c_void_p()
     _check(lib, lib.ac_resolve_bridge_paths(ent, offs, len(paths), cw, w, nw, device, C.byref(h)))
     return _resolve_result(lib, h)
+
+
+class Components:
+    """What ac_graph_components / ac_components_from_links found, copied out of the handle (numpy arrays):
+    records        structured array, one per component in connected_components() order: first, unitigs, length, links_all, links_one_way,
+                   open_ends, marked, circular_loop
+    component_of   per unitig its component index; NOT_ALIVE for a unitig that is not alive
+    member_off, members   component c = members[member_off[c] : member_off[c + 1]], unitig numbers ascending
+    flags          per unitig: OPEN_START, OPEN_END, HAIRPIN_START, HAIRPIN_END, ISOLATED_CIRCULAR, ISOLATED_LINEAR
+    summary        dict (unitigs = the alive ones, components, topology, links_all, links_one_way, total_length, launches, read_backs,
+                   seconds_device); topology: the reference's string"""
+    NOT_ALIVE = 0xFFFFFFFF
+    OPEN_START, OPEN_END, HAIRPIN_START, HAIRPIN_END, ISOLATED_CIRCULAR, ISOLATED_LINEAR = 1, 2, 4, 8, 16, 32
+
+    def __init__(self, lib, h, n_unitigs):
+        import numpy as np
+        try:
+            dt = np.dtype([("first", "<u4"), ("unitigs", "<u4"), ("length", "<u8"), ("links_all", "<u8"), ("links_one_way", "<u8"),
+                           ("open_ends", "<u4"), ("marked", "<u4"), ("circular_loop", "u1")], align=True)
+            assert dt.itemsize == C.sizeof(Component)
+
+            def take(ptr, n, dtype):
+                dtype = np.dtype(dtype)
+                return np.frombuffer(C.string_at(ptr, n * dtype.itemsize), dtype=dtype) if n else np.zeros(0, dtype=dtype)
+            rp, rn = C.POINTER(Component)(), C.c_uint32()
+            _check(lib, lib.ac_components_records(h, C.byref(rp), C.byref(rn)))
+            self.records = take(rp, rn.value, dt)
+            cp = C.POINTER(C.c_uint32)()
+            _check(lib, lib.ac_components_of_unitig(h, C.byref(cp)))
+            self.component_of = take(cp, n_unitigs, "<u4")
+            op, mp = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+            _check(lib, lib.ac_components_members(h, C.byref(op), C.byref(mp)))
+            self.member_off = take(op, rn.value + 1, "<u8")
+            self.members = take(mp, int(self.member_off[-1]), "<u4")
+            fp = C.POINTER(C.c_uint8)()
+            _check(lib, lib.ac_components_unitig_flags(h, C.byref(fp)))
+            self.flags = take(fp, n_unitigs, "u1")
+            sm = ComponentsSummary()
+            assert lib.ac_components_summary_get_sized(h, C.byref(sm), C.sizeof(ComponentsSummary)) == C.sizeof(ComponentsSummary) == sm.size
+            self.summary = sm.as_dict()
+            self.topology = lib.ac_topology_name(sm.topology).decode()
+        finally:
+            lib.ac_components_free(h)
+
+    def components(self):
+        """connected_components(): a list of ascending member lists"""
+        off, m = self.member_off.tolist(), self.members.tolist()
+        return [m[off[c]:off[c + 1]] for c in range(len(off) - 1)]
+
+    def record_dicts(self):
+        return [{k: int(r[k]) for k in self.records.dtype.names} for r in self.records]
+
+
+def _bytes_per_unitig(values, n, what):
+    """None, or one byte per unitig (any sequence of truth values, or a numpy array)"""
+    if values is None:
+        return None
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(values) != 0, dtype=np.uint8)
+    if a.shape != (n,):
+        raise AutocyclerError(f"{what}: one entry per unitig expected ({n}), got shape {a.shape}")
+    return a
+
+
+def graph_components(graph, marked=None, device=0, lib_path=None):
+    """ac_graph_components: connected components, circular loops, link counts and topology of a Graph's links (one entry per L line) and
+    unitig lengths.  marked: one truth value per unitig, counted per component.  lib_path is not needed: the graph knows its library."""
+    lib = graph._lib
+    n = graph.unitig_count
+    mk = _bytes_per_unitig(marked, n, "marked")
+    h = C.c_void_p()
+    _check(lib, lib.ac_graph_components(graph._h, mk.ctypes.data if mk is not None else None, device, C.byref(h)))
+    return Components(lib, h, n)
+
+
+def components_from_links(n_unitigs, links, unitig_len=None, alive=None, marked=None, device=0, lib_path=None):
+    """ac_components_from_links: the same on plain arrays.  links: (a, b) pairs of signed unitig numbers (a list, or an (m, 2) int32 numpy
+    array) in L-line order; unitig_len[u - 1] = length of unitig u; alive: the unitigs that are still there (None = all) — one that is not
+    is in no component and its links are ignored."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+    ln = None
+    if unitig_len is not None:
+        ln = np.ascontiguousarray(np.asarray(unitig_len, dtype=np.uint32))
+        if ln.shape != (n_unitigs,):
+            raise AutocyclerError(f"unitig_len: one entry per unitig expected ({n_unitigs}), got shape {ln.shape}")
+    al, mk = _bytes_per_unitig(alive, n_unitigs, "alive"), _bytes_per_unitig(marked, n_unitigs, "marked")
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_components_from_links(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(mk), device, C.byref(h)))
+    return Components(lib, h, n_unitigs)
 
 
 class ClusterTree:

@@ -1,6 +1,7 @@
 // C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, resolve, cluster, read depths, the
 // verifier, decompress, the GFA reload, and the self-tests of the device primitives.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -235,6 +236,80 @@ size_t ac_resolve_summary_get_sized(const ac_resolve* r, ac_resolve_summary* out
 }
 uint32_t ac_resolve_max_path(void) { return resolve_max_path(); }
 void ac_resolve_free(ac_resolve* r) { delete r; }
+
+// ---- connected components and topology: the analysis on the device (kernels_components.inc), totals and the topology chain on the host
+// (components_host.cpp).  Read-only: the graph edits that rest on it stay with the caller ----
+struct ac_components {
+    ComponentsResult r;
+    ac_components_summary summary;
+};
+static_assert(sizeof(ac_component) == sizeof(ComponentRecord) && offsetof(ac_component, length) == offsetof(ComponentRecord, length) &&
+              offsetof(ac_component, marked) == offsetof(ComponentRecord, marked) && offsetof(ac_component, circular_loop) == offsetof(ComponentRecord, circular_loop),
+              "ac_component and ComponentRecord are one layout");
+static_assert(sizeof(ac_link) == sizeof(Link), "ac_link and Link are one layout");
+static void components_run(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
+                           int device, ac_components** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (n_links && !links) throw DeviceError("null pointer: n_links > 0 without links");
+    auto h = std::make_unique<ac_components>();
+    if (n_unitigs == 0 && n_links == 0) {      // (nothing to launch: no device is asked for)
+        h->r.member_off.assign(1, 0);
+        components_finish(&h->r);
+    } else {
+        DeviceCall call(device);
+        components_device(n_unitigs, (const Link*)links, n_links, unitig_len, alive, marked, &h->r);
+    }
+    ac_components_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.unitigs = h->r.alive; sm.components = (uint32_t)h->r.records.size(); sm.topology = h->r.topology;
+    sm.links_all = h->r.links_all; sm.links_one_way = h->r.links_one_way; sm.total_length = h->r.total_length;
+    sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+    *out = h.release();
+}
+int ac_components_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
+                             int device, ac_components** out) {
+    return guarded([&] { components_run(n_unitigs, links, n_links, unitig_len, alive, marked, device, out); });
+}
+int ac_graph_components(const ac_graph* g, const uint8_t* marked, int device, ac_components** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        components_run(g->g.n_unitigs, (const ac_link*)g->g.links, g->g.n_links, g->g.seq_len, nullptr, marked, device, out);
+    });
+}
+int ac_components_records(const ac_components* c, const ac_component** records, uint32_t* n) {
+    return guarded([&] {
+        if (!c || !records || !n) throw DeviceError("null pointer");
+        *records = (const ac_component*)c->r.records.data(); *n = (uint32_t)c->r.records.size();
+    });
+}
+int ac_components_of_unitig(const ac_components* c, const uint32_t** component) {
+    return guarded([&] {
+        if (!c || !component) throw DeviceError("null pointer");
+        *component = c->r.component_of.data();
+    });
+}
+int ac_components_members(const ac_components* c, const uint64_t** off, const uint32_t** members) {
+    return guarded([&] {
+        if (!c || !off || !members) throw DeviceError("null pointer");
+        *off = c->r.member_off.data(); *members = c->r.members.data();
+    });
+}
+int ac_components_unitig_flags(const ac_components* c, const uint8_t** flags) {
+    return guarded([&] {
+        if (!c || !flags) throw DeviceError("null pointer");
+        *flags = c->r.flags.data();
+    });
+}
+size_t ac_components_summary_get_sized(const ac_components* c, ac_components_summary* out, size_t out_size) {
+    if (c && out) memcpy(out, &c->summary, std::min(out_size, sizeof(ac_components_summary)));
+    return sizeof(ac_components_summary);
+}
+const char* ac_topology_name(uint32_t topology) { return components_topology_name(topology); }
+void ac_components_free(ac_components* c) { delete c; }
 
 // ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
 // from it on the host (cluster_host.cpp); the QC verdicts, scores and refinement further down.  Writing the clusters stays with the caller ----

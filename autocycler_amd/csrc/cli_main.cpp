@@ -1,6 +1,7 @@
 // autocycler-compress — standalone driver with the flag surface of `autocycler compress` (main.rs:140-160):
-//   -i/--assemblies_dir DIR  -a/--autocycler_dir DIR  [--kmer 51] [--max_contigs 25] [-t/--threads 8] [--device 0 | --devices 0,1,..]
-// (--devices: one job over several GPUs of the node through ac_compress_build_multi; not a flag of the reference)
+//   -i/--assemblies_dir DIR  -a/--autocycler_dir DIR  [--kmer 51] [--max_contigs 25] [-t/--threads 8] [--device 0 | --devices 0,1,..] [--stats]
+// (--devices: one job over several GPUs of the node through ac_compress_build_multi; --stats: the graph's connected components and
+// topology after the usual lines, ac_graph_components; neither is a flag of the reference)
 // Writes DIR/input_assemblies.gfa and DIR/input_assemblies.yaml (compress.rs:45-46) through the C ABI
 // (ac_compress_dir: C++ loader + end repair, HIP graph build, host tail, buffered GFA writer).
 #include <chrono>
@@ -14,7 +15,7 @@
 #include "../../include/autocycler_hip.h"
 
 static void usage() {
-    fprintf(stderr, "Usage: autocycler-compress --assemblies_dir <DIR> --autocycler_dir <DIR> [--kmer 51] [--max_contigs 25] [--threads 8] [--device 0 | --devices 0,1,..]\n");
+    fprintf(stderr, "Usage: autocycler-compress --assemblies_dir <DIR> --autocycler_dir <DIR> [--kmer 51] [--max_contigs 25] [--threads 8] [--device 0 | --devices 0,1,..] [--stats]\n");
 }
 
 // `autocycler decompress` (main.rs:163-175): -i/--in_gfa FILE  [-o/--out_dir DIR]  [-f/--out_file FASTA]
@@ -46,6 +47,7 @@ int main(int argc, char** argv) {
     std::string in, out;
     unsigned k = 51, max_contigs = 25;
     int threads = 8, device = 0;
+    bool stats = false;
     std::vector<int> devices;
     int i = 1;
     if (argc > 1 && strcmp(argv[1], "compress") == 0) i = 2;
@@ -62,6 +64,7 @@ int main(int argc, char** argv) {
         else if (a == "-t" || a == "--threads") threads = atoi(val());
         else if (a == "--device") device = atoi(val());
         else if (a == "--devices") { const char* v = val(); for (const char* q = v; *q;) { devices.push_back(atoi(q)); while (*q && *q != ',') q++; if (*q == ',') q++; } }
+        else if (a == "--stats") stats = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
     }
@@ -83,6 +86,14 @@ int main(int argc, char** argv) {
             (unsigned long long)pre.links_one_way, pre.links_one_way == 1 ? "" : "s", (unsigned long long)pre.total_length);
     fprintf(stderr, "%u unitig%s, %llu link%s\ntotal length: %llu bp\n\n", post.unitigs, post.unitigs == 1 ? "" : "s",
             (unsigned long long)post.links_one_way, post.links_one_way == 1 ? "" : "s", (unsigned long long)post.total_length);
+    if (stats) {
+        ac_components* c = nullptr;
+        ac_components_summary sm;
+        if (ac_graph_components(g, nullptr, devices.empty() ? device : devices[0], &c) != 0) { fprintf(stderr, "\nError: %s\n", ac_last_error()); return 1; }
+        ac_components_summary_get_sized(c, &sm, sizeof sm);
+        fprintf(stderr, "%u connected component%s (%s)\n\n", sm.components, sm.components == 1 ? "" : "s", ac_topology_name(sm.topology));
+        ac_components_free(c);
+    }
     ac_free(g);
     double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     fprintf(stderr, "Compressed unitig graph: %s/input_assemblies.gfa\nInput assembly stats:    %s/input_assemblies.yaml\n", out.c_str(), out.c_str());

@@ -14,6 +14,7 @@
 #include "graph_types.hpp"
 #include "trim_host.hpp"
 #include "resolve_host.hpp"
+#include "components_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -210,6 +211,11 @@ struct ClusterQcDeviceStats {
 };
 void cluster_qc_device(const double* asym, uint32_t n, const uint32_t* dfs_tip, double cutoff, const std::function<void(const ClusterQcEvaluate&)>& body,
                        ClusterQcDeviceStats* st);
+// connected_components / component_is_circular_loop / link_count / topology (unitig_graph.rs:478-545, 905-967) on the device
+// (kernels_components.inc): links as ac_links hands them out, unitig_len / alive / marked one entry per unitig or null; totals and
+// topology are components_host.cpp's.
+void components_device(uint32_t n_unitigs, const Link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
+                       ComponentsResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

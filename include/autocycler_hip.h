@@ -480,6 +480,60 @@ int ac_path_distances(const int32_t* entries, const uint64_t* path_off, uint32_t
                       uint64_t n_pairs, const uint32_t* weights, uint32_t n_weights, int device, uint32_t* dist, uint8_t* status);
 uint32_t ac_resolve_max_path(void);   /* 65536 entries: the longest path a distance job takes */
 
+/* Connected components and graph topology: UnitigGraph::connected_components, component_is_circular_loop, link_count and topology
+ * (unitig_graph.rs:478-545, 905-967) with the per-unitig end tests of unitig.rs:197-215, 276-293 — what resolve deletes components by
+ * (resolve.rs:273-282), what merge_linear_paths starts from (fix_circular_loops, graph_simplification.rs:374-384) and what combine and
+ * gfa2fasta print per unitig.  Read-only: no graph is edited here.
+ * The graph is what build_links_from_gfa (unitig_graph.rs:91-115) makes of the link entries in their order: an entry (a, b) puts b into a's
+ * next list (forward_next for a > 0, reverse_next otherwise) and a into b's prev list (forward_prev for b > 0, reverse_prev otherwise).
+ * Entries may repeat (list lengths count repeats, link_count does not: it is two sets) and their reverse complements may be missing.  Two
+ * unitigs are connected when any of the four lists of one names the other.  Components come in connected_components() order — ascending
+ * lowest member — and their members ascend.  circular_loop is the literal walk of unitig_graph.rs:949-967 from (first, +): among its
+ * consequences a single unitig with a hairpin link at both ends is a "loop".
+ * Everything runs on the device in a number of launches that grows with log2(n_unitigs) only, never with the graph's diameter or its
+ * number of components; the host reads a 48-byte header once the last kernel is done and then the results, sized by it.
+ * Errors (return 1, ac_last_error), never faults: a link that names unitig 0 or one above n_unitigs (the first such entry is quoted), NULL
+ * out, n_links > 0 without links, a handle without host arrays.  n_unitigs == 0 is a valid, empty result (topology "empty"). */
+typedef struct ac_components ac_components;
+typedef struct {
+    uint32_t first;          /* lowest member = the reference's component[0] */
+    uint32_t unitigs;
+    uint64_t length;         /* sum of member lengths; 0 when no lengths were given */
+    uint64_t links_all;      /* link_count() restricted to this component: .0 */
+    uint64_t links_one_way;  /*                                            .1 */
+    uint32_t open_ends;      /* unitig ends whose next list is empty (open_start + open_end over members) */
+    uint32_t marked;         /* members with marked[u-1] != 0 */
+    uint8_t  circular_loop;  /* component_is_circular_loop(members ascending) */
+} ac_component;
+typedef struct {
+    uint32_t size;           /* the library's sizeof(ac_components_summary) */
+    uint32_t unitigs, components, topology;   /* unitigs: the alive ones; topology: AC_TOPOLOGY_* over them */
+    uint64_t links_all, links_one_way, total_length;
+    uint32_t launches, read_backs;   /* kernel launches (fused fills and the read-back's own kernel included) and host round trips of the call */
+    double seconds_device;   /* first kernel to last, by device events */
+} ac_components_summary;
+enum { AC_TOPOLOGY_EMPTY, AC_TOPOLOGY_FRAGMENTED, AC_TOPOLOGY_LINEAR_OPEN_OPEN, AC_TOPOLOGY_CIRCULAR,
+       AC_TOPOLOGY_LINEAR_HAIRPIN_HAIRPIN, AC_TOPOLOGY_LINEAR_OPEN_HAIRPIN, AC_TOPOLOGY_OTHER };
+/* On the links (ac_links: one entry per L line) and unitig lengths of a graph handle (a build, or ac_graph_from_gfa).  marked: one byte
+ * per unitig or NULL; ac_component.marked counts them per component (e.g. the anchors of ac_resolve_anchors: a component with marked == 0
+ * is what delete_unitigs_not_connected_to_anchor removes). */
+int ac_graph_components(const ac_graph*, const uint8_t* marked /* n_unitigs, or NULL */, int device, ac_components** out);
+/* The same on the caller's arrays, for a graph that has been edited.  alive: the reference's removed unitigs without renumbering — a unitig
+ * that is not alive is in no component and every link touching it is ignored (remove_unitigs_by_number + delete_dangling_links). */
+int ac_components_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links,
+                             const uint32_t* unitig_len /* or NULL */, const uint8_t* alive /* or NULL = all */,
+                             const uint8_t* marked /* or NULL */, int device, ac_components** out);
+/* The arrays belong to the handle. */
+int ac_components_records(const ac_components*, const ac_component** records, uint32_t* n);      /* in connected_components() order */
+int ac_components_of_unitig(const ac_components*, const uint32_t** component /* n_unitigs; UINT32_MAX = not alive */);
+int ac_components_members(const ac_components*, const uint64_t** off /* n + 1 */, const uint32_t** members /* ascending in each */);
+/* 1 open_start, 2 open_end, 4 hairpin_start, 8 hairpin_end, 16 is_isolated_and_circular, 32 is_isolated_and_linear; 0 when not alive */
+int ac_components_unitig_flags(const ac_components*, const uint8_t** flags);
+/* at most out_size bytes are written (the struct only grows at its end); returns the library's sizeof(ac_components_summary) */
+size_t ac_components_summary_get_sized(const ac_components*, ac_components_summary* out, size_t out_size);
+const char* ac_topology_name(uint32_t topology);    /* the reference's strings: "circular", "linear-open-hairpin", ...; NULL beyond AC_TOPOLOGY_OTHER */
+void ac_components_free(ac_components*);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -773,8 +827,11 @@ const char* ac_version(void);
  *      ac_cluster_qc_metrics, ac_cluster_qc_trace, ac_cluster_qc_summary_get_sized, ac_cluster_qc_free, ac_cluster_min_assemblies,
  *      ac_cluster_seq_inputs with ac_cluster_qc_record, ac_clustering_metrics and ac_cluster_qc_summary.
  *  11: additions only: the runtime's test hooks ac_selftest_fills, ac_selftest_fill_order, ac_selftest_readback, ac_selftest_scalar_chain,
- *      ac_selftest_arena, ac_selftest_launch, ac_selftest_atomics, ac_selftest_side_order, ac_selftest_event_ring. */
-#define AC_ABI_VERSION 11
+ *      ac_selftest_arena, ac_selftest_launch, ac_selftest_atomics, ac_selftest_side_order, ac_selftest_event_ring.
+ *  12: additions only: ac_graph_components, ac_components_from_links, ac_components_records, ac_components_of_unitig,
+ *      ac_components_members, ac_components_unitig_flags, ac_components_summary_get_sized, ac_topology_name, ac_components_free with
+ *      ac_component, ac_components_summary and the AC_TOPOLOGY_* values. */
+#define AC_ABI_VERSION 12
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
