@@ -110,6 +110,19 @@ class ComponentsSummary(C.Structure):      # ac_components_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class MergeChain(C.Structure):      # ac_merge_chain
+    _fields_ = [("number", C.c_uint32), ("members", C.c_uint32), ("length", C.c_uint64), ("member_off", C.c_uint64), ("seq_off", C.c_uint64), ("depth", C.c_double),
+                ("type", C.c_uint8), ("loop", C.c_uint8)]
+
+
+class MergeSummary(C.Structure):      # ac_merge_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "chains", "merged_unitigs", "unitigs_after")] + [("links_after", C.c_uint64), ("bases_copied", C.c_uint64)] + \
+               [("launches", C.c_uint32), ("read_backs", C.c_uint32), ("seconds_device", C.c_double), ("seconds_copy", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -168,7 +181,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -270,6 +283,19 @@ def load_library(path=None):
     lib.ac_topology_name.argtypes = [C.c_uint32]
     lib.ac_components_free.argtypes = [C.c_void_p]
     lib.ac_components_free.restype = None
+    lib.ac_graph_merge_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_merge_plan_from_links.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_merge_chains.argtypes = [C.c_void_p, C.POINTER(C.POINTER(MergeChain)), C.POINTER(C.c_uint32)]
+    lib.ac_merge_members.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_uint64)]
+    lib.ac_merge_chain_of_unitig.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32))]
+    lib.ac_merge_fixed_flags.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8))]
+    lib.ac_merge_sequences.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+    lib.ac_merge_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Link)), C.POINTER(C.c_uint64)]
+    lib.ac_merge_summary_get_sized.restype = C.c_size_t
+    lib.ac_merge_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(MergeSummary), C.c_size_t]
+    lib.ac_merge_free.argtypes = [C.c_void_p]
+    lib.ac_merge_free.restype = None
     lib.ac_cluster_max_seqs.restype = C.c_uint32
     lib.ac_cluster_max_seqs.argtypes = []
     lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -752,6 +778,114 @@ def components_from_links(n_unitigs, links, unitig_len=None, alive=None, marked=
     h = C.c_void_p()
     _check(lib, lib.ac_components_from_links(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(mk), device, C.byref(h)))
     return Components(lib, h, n_unitigs)
+
+
+class MergePlan:
+    """What ac_graph_merge_plan / ac_merge_plan_from_links found, copied out of the handle (numpy arrays):
+    chains         structured array, one per chain in the order merge_linear_paths finds them: number, members, length, member_off, seq_off,
+                   depth, type (OTHER or CONSENTIG), loop
+    members        signed unitig numbers in path order: chain c = members[member_off : member_off + members]
+    chain_of       per unitig its chain index; NOT_MERGED
+    fixed          per unitig: FIXED_START, FIXED_END (after fix_circular_loops)
+    sequences      the merged bytes: chain c = sequences[seq_off : seq_off + length] (empty when none were given or asked for)
+    links          (m, 2) int32: the link set after the merge, ascending by (a, b) — a set, not get_links_for_gfa order
+    summary        dict (chains, merged_unitigs, unitigs_after, links_after, bases_copied, launches, read_backs, seconds_device, seconds_copy)"""
+    NOT_MERGED = 0xFFFFFFFF
+    FIXED_START, FIXED_END = 1, 2
+    OTHER, ANCHOR, CONSENTIG, BRIDGE = 0, 1, 2, 3
+
+    def __init__(self, lib, h, n_unitigs):
+        import numpy as np
+        try:
+            dt = np.dtype([("number", "<u4"), ("members", "<u4"), ("length", "<u8"), ("member_off", "<u8"), ("seq_off", "<u8"), ("depth", "<f8"), ("type", "u1"),
+                           ("loop", "u1")], align=True)
+            assert dt.itemsize == C.sizeof(MergeChain)
+
+            def take(ptr, n, dtype):
+                dtype = np.dtype(dtype)
+                return np.frombuffer(C.string_at(ptr, n * dtype.itemsize), dtype=dtype) if n else np.zeros(0, dtype=dtype)
+            rp, rn = C.POINTER(MergeChain)(), C.c_uint32()
+            _check(lib, lib.ac_merge_chains(h, C.byref(rp), C.byref(rn)))
+            self.chains = take(rp, rn.value, dt)
+            mp, mn = C.POINTER(C.c_int32)(), C.c_uint64()
+            _check(lib, lib.ac_merge_members(h, C.byref(mp), C.byref(mn)))
+            self.members = take(mp, mn.value, "<i4")
+            cp = C.POINTER(C.c_uint32)()
+            _check(lib, lib.ac_merge_chain_of_unitig(h, C.byref(cp)))
+            self.chain_of = take(cp, n_unitigs, "<u4")
+            fp = C.POINTER(C.c_uint8)()
+            _check(lib, lib.ac_merge_fixed_flags(h, C.byref(fp)))
+            self.fixed = take(fp, n_unitigs, "u1")
+            sp, sn = C.POINTER(C.c_uint8)(), C.c_uint64()
+            _check(lib, lib.ac_merge_sequences(h, C.byref(sp), C.byref(sn)))
+            self.sequences = take(sp, sn.value, "u1")
+            lp, ln = C.POINTER(Link)(), C.c_uint64()
+            _check(lib, lib.ac_merge_links(h, C.byref(lp), C.byref(ln)))
+            self.links = take(lp, 2 * ln.value, "<i4").reshape(-1, 2)
+            sm = MergeSummary()
+            assert lib.ac_merge_summary_get_sized(h, C.byref(sm), C.sizeof(MergeSummary)) == C.sizeof(MergeSummary) == sm.size
+            self.summary = sm.as_dict()
+        finally:
+            lib.ac_merge_free(h)
+
+    def chain_members(self):
+        """merge_paths: a list of lists of signed unitig numbers"""
+        m = self.members.tolist()
+        return [m[int(c["member_off"]):int(c["member_off"]) + int(c["members"])] for c in self.chains]
+
+    def chain_sequences(self):
+        b = self.sequences.tobytes()
+        return [b[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])] for c in self.chains] if len(b) else []
+
+    def chain_dicts(self):
+        return [{k: (float(r[k]) if k == "depth" else int(r[k])) for k in self.chains.dtype.names} for r in self.chains]
+
+
+def graph_merge_plan(graph, use_paths=True, with_sequences=True, device=0, lib_path=None):
+    """ac_graph_merge_plan: what merge_linear_paths would do to a Graph, and its products.  use_paths: the path ends fix unitig ends and the
+    position counts come from the paths (the reference's call with the graph's sequences); False: a call without sequences on a graph without
+    positions.  lib_path is not needed: the graph knows its library."""
+    lib = graph._lib
+    h = C.c_void_p()
+    _check(lib, lib.ac_graph_merge_plan(graph._h, int(bool(use_paths)), int(bool(with_sequences)), device, C.byref(h)))
+    return MergePlan(lib, h, graph.unitig_count)
+
+
+def merge_plan_from_links(n_unitigs, links, unitig_len, alive=None, path_ends=None, depth=None, fwd_positions=None, rev_positions=None, unitig_type=None,
+                          sequences=None, device=0, lib_path=None):
+    """ac_merge_plan_from_links: the same on plain arrays.  links: (a, b) pairs of signed unitig numbers, a set closed under reverse
+    complement; path_ends: (first, last) signed entries per sequence; fwd_positions / rev_positions: position counts per unitig;
+    unitig_type: MergePlan.OTHER / ANCHOR / CONSENTIG / BRIDGE per unitig; sequences: one bytes object per unitig (forward strand), or a
+    tuple (all bytes as a uint8 array, the first byte of every unitig as a uint64 array)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+
+    def per_unitig(values, dtype, what):
+        if values is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+        if a.shape != (n_unitigs,):
+            raise AutocyclerError(f"{what}: one entry per unitig expected ({n_unitigs}), got shape {a.shape}")
+        return a
+    ln, dp = per_unitig(unitig_len, np.uint32, "unitig_len"), per_unitig(depth, np.float64, "depth")
+    fw, rv = per_unitig(fwd_positions, np.uint32, "fwd_positions"), per_unitig(rev_positions, np.uint32, "rev_positions")
+    ty, al = per_unitig(unitig_type, np.uint8, "unitig_type"), _bytes_per_unitig(alive, n_unitigs, "alive")
+    pe = np.ascontiguousarray(np.asarray(path_ends, dtype=np.int32).reshape(-1, 2)) if path_ends is not None else np.zeros((0, 2), dtype=np.int32)
+    sb = sg = None
+    if isinstance(sequences, tuple):      # (bytes of all forward sequences as a uint8 array, first byte per unitig as a uint64 array)
+        sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), per_unitig(sequences[1], np.uint64, "sequences[1]")
+    elif sequences is not None:
+        if len(sequences) != n_unitigs:
+            raise AutocyclerError(f"sequences: one entry per unitig expected ({n_unitigs}), got {len(sequences)}")
+        sg = np.zeros(max(n_unitigs, 1), dtype=np.uint64)
+        sg[1:n_unitigs] = np.cumsum([len(x) for x in sequences[:-1]], dtype=np.uint64) if n_unitigs > 1 else []
+        sb = np.frombuffer(b"".join(bytes(x) for x in sequences) + b"\0", dtype=np.uint8)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_merge_plan_from_links(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(pe), pe.shape[0], ptr(dp), ptr(fw), ptr(rv), ptr(ty),
+                                             ptr(sb), ptr(sg), device, C.byref(h)))
+    return MergePlan(lib, h, n_unitigs)
 
 
 class ClusterTree:

@@ -311,6 +311,121 @@ size_t ac_components_summary_get_sized(const ac_components* c, ac_components_sum
 const char* ac_topology_name(uint32_t topology) { return components_topology_name(topology); }
 void ac_components_free(ac_components* c) { delete c; }
 
+// ---- the linear-path merge plan: chains, members, sequences and the link set after the merge on the device (kernels_merge.inc); the fixed
+// seeds, depths, types and totals on the host (merge_host.cpp).  Read-only: applying the plan to a graph stays with the caller ----
+struct ac_merge {
+    MergeResult r;
+    ac_merge_summary summary;
+};
+static_assert(sizeof(ac_merge_chain) == sizeof(MergeChainRecord) && offsetof(ac_merge_chain, length) == offsetof(MergeChainRecord, length) &&
+              offsetof(ac_merge_chain, seq_off) == offsetof(MergeChainRecord, seq_off) && offsetof(ac_merge_chain, depth) == offsetof(MergeChainRecord, depth) &&
+              offsetof(ac_merge_chain, type) == offsetof(MergeChainRecord, type) && offsetof(ac_merge_chain, loop) == offsetof(MergeChainRecord, loop),
+              "ac_merge_chain and MergeChainRecord are one layout");
+static_assert(sizeof(ac_link) == sizeof(MergeLink), "ac_link and MergeLink are one layout");
+static_assert((int)AC_UNITIG_OTHER == (int)MERGE_TYPE_OTHER && (int)AC_UNITIG_ANCHOR == (int)MERGE_TYPE_ANCHOR &&
+              (int)AC_UNITIG_CONSENTIG == (int)MERGE_TYPE_CONSENTIG && (int)AC_UNITIG_BRIDGE == (int)MERGE_TYPE_BRIDGE, "the AC_UNITIG_* values are merge_host.hpp's");
+// path: the signed entries whose histogram gives the position counts (a handle with use_paths), or null: fwd / rev are the caller's
+static void merge_run(uint32_t n, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path_ends, uint32_t n_seqs,
+                      const double* depth, const uint32_t* fwd, const uint32_t* rev, const uint8_t* type, const uint8_t* seq_bytes, const uint64_t* seq_begin,
+                      uint64_t seq_total, const int32_t* path, uint64_t n_path, int device, ac_merge** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (n_links && !links) throw DeviceError("null pointer: n_links > 0 without links");
+    if (n && !unitig_len) throw DeviceError("null pointer: unitig_len");
+    if ((seq_bytes == nullptr) != (seq_begin == nullptr)) throw DeviceError("seq_bytes and seq_begin: both or neither");
+    if (n_seqs && !path_ends) throw DeviceError("null pointer: n_seqs > 0 without path_ends");
+    if ((fwd == nullptr) != (rev == nullptr)) throw DeviceError("fwd_positions and rev_positions: both or neither");
+    auto h = std::make_unique<ac_merge>();
+    std::vector<uint8_t> seed;
+    merge_seed_fixed(n, alive, path_ends, n_seqs, &seed);
+    if (n == 0 && n_links == 0) {      // (nothing to launch: no device is asked for)
+        merge_finish(&h->r, unitig_len, alive, depth, fwd, rev, type);
+    } else {
+        MergePlanInput in;
+        in.n_unitigs = n; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.alive = alive; in.seed_fixed = seed.data();
+        in.path = path; in.n_path = n_path; in.seq_bytes = seq_bytes; in.seq_begin = seq_begin; in.seq_total = seq_total;
+        DeviceCall call(device);
+        merge_plan_device(in, &h->r);
+        if (path && n_path) { fwd = h->r.fwd_positions.data(); rev = h->r.rev_positions.data(); }
+        merge_finish(&h->r, unitig_len, alive, depth, fwd, rev, type);
+    }
+    ac_merge_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.chains = (uint32_t)h->r.chains.size(); sm.merged_unitigs = h->r.merged_unitigs; sm.unitigs_after = h->r.unitigs_after;
+    sm.links_after = h->r.links.size(); sm.bases_copied = h->r.bases_copied; sm.launches = h->r.launches; sm.read_backs = h->r.read_backs;
+    sm.seconds_device = h->r.seconds_device; sm.seconds_copy = h->r.seconds_copy;
+    *out = h.release();
+}
+int ac_merge_plan_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path_ends,
+                             uint32_t n_seqs, const double* depth, const uint32_t* fwd_positions, const uint32_t* rev_positions, const uint8_t* type,
+                             const uint8_t* seq_bytes, const uint64_t* seq_begin, int device, ac_merge** out) {
+    return guarded([&] {
+        uint64_t seq_total = 0;      // the bytes behind seq_bytes: up to the end of the last unitig
+        if (seq_bytes && seq_begin && unitig_len)
+            for (uint32_t u = 0; u < n_unitigs; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + unitig_len[u]);
+        merge_run(n_unitigs, links, n_links, unitig_len, alive, path_ends, n_seqs, depth, fwd_positions, rev_positions, type, seq_bytes, seq_begin, seq_total, nullptr, 0,
+                  device, out);
+    });
+}
+int ac_graph_merge_plan(const ac_graph* g, int use_paths, int with_sequences, int device, ac_merge** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays || (use_paths && !g->host_paths)) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const FinalGraph& f = g->g;
+        std::vector<int32_t> ends;      // first and last entry of every non-empty path
+        if (use_paths)
+            for (size_t s = 0; s + 1 < f.path_off.size(); s++)
+                if (f.path_off[s + 1] > f.path_off[s]) { ends.push_back(f.path[f.path_off[s]]); ends.push_back(f.path[f.path_off[s + 1] - 1]); }
+        const bool seqs = with_sequences && f.seq_block.p && f.seq_begin;
+        merge_run(f.n_unitigs, (const ac_link*)f.links, f.n_links, f.seq_len, nullptr, ends.data(), (uint32_t)(ends.size() / 2), f.depth, nullptr, nullptr, nullptr,
+                  seqs ? (const uint8_t*)f.seq_block.p : nullptr, seqs ? f.seq_begin : nullptr, seqs ? f.seq_block.bytes : 0, use_paths ? f.path : nullptr,
+                  use_paths ? f.n_path : 0, device, out);
+    });
+}
+int ac_merge_chains(const ac_merge* m, const ac_merge_chain** chains, uint32_t* n) {
+    return guarded([&] {
+        if (!m || !chains || !n) throw DeviceError("null pointer");
+        *chains = (const ac_merge_chain*)m->r.chains.data(); *n = (uint32_t)m->r.chains.size();
+    });
+}
+int ac_merge_members(const ac_merge* m, const int32_t** members, uint64_t* n) {
+    return guarded([&] {
+        if (!m || !members || !n) throw DeviceError("null pointer");
+        *members = m->r.members.data(); *n = m->r.members.size();
+    });
+}
+int ac_merge_chain_of_unitig(const ac_merge* m, const uint32_t** chain) {
+    return guarded([&] {
+        if (!m || !chain) throw DeviceError("null pointer");
+        *chain = m->r.chain_of.data();
+    });
+}
+int ac_merge_fixed_flags(const ac_merge* m, const uint8_t** flags) {
+    return guarded([&] {
+        if (!m || !flags) throw DeviceError("null pointer");
+        *flags = m->r.fixed.data();
+    });
+}
+int ac_merge_sequences(const ac_merge* m, const uint8_t** bytes, uint64_t* n) {
+    return guarded([&] {
+        if (!m || !bytes || !n) throw DeviceError("null pointer");
+        *bytes = m->r.seq.data(); *n = m->r.seq.size();
+    });
+}
+int ac_merge_links(const ac_merge* m, const ac_link** links, uint64_t* n) {
+    return guarded([&] {
+        if (!m || !links || !n) throw DeviceError("null pointer");
+        *links = (const ac_link*)m->r.links.data(); *n = m->r.links.size();
+    });
+}
+size_t ac_merge_summary_get_sized(const ac_merge* m, ac_merge_summary* out, size_t out_size) {
+    if (m && out) memcpy(out, &m->summary, std::min(out_size, sizeof(ac_merge_summary)));
+    return sizeof(ac_merge_summary);
+}
+void ac_merge_free(ac_merge* m) { delete m; }
+
 // ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
 // from it on the host (cluster_host.cpp); the QC verdicts, scores and refinement further down.  Writing the clusters stays with the caller ----
 struct ac_cluster_tree {

@@ -15,6 +15,7 @@
 #include "trim_host.hpp"
 #include "resolve_host.hpp"
 #include "components_host.hpp"
+#include "merge_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -216,6 +217,16 @@ void cluster_qc_device(const double* asym, uint32_t n, const uint32_t* dfs_tip, 
 // topology are components_host.cpp's.
 void components_device(uint32_t n_unitigs, const Link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
                        ComponentsResult* out);
+// The linear-path merge plan (graph_simplification.rs:315-371, 410-485) on the device (kernels_merge.inc): chains, members, merged sequences
+// and the link set after the merge; numbers, depths, types and totals are merge_host.cpp's.  seed_fixed: merge_seed_fixed's bytes;
+// path: the signed path entries whose histogram gives the position counts (or null); seq_bytes / seq_begin: both or neither, seq_total =
+// the bytes behind seq_bytes.
+struct MergePlanInput {
+    uint32_t n_unitigs = 0; const Link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const uint8_t* alive = nullptr;
+    const uint8_t* seed_fixed = nullptr; const int32_t* path = nullptr; uint64_t n_path = 0;
+    const uint8_t* seq_bytes = nullptr; const uint64_t* seq_begin = nullptr; uint64_t seq_total = 0;
+};
+void merge_plan_device(const MergePlanInput& in, MergeResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

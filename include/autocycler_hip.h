@@ -534,6 +534,65 @@ size_t ac_components_summary_get_sized(const ac_components*, ac_components_summa
 const char* ac_topology_name(uint32_t topology);    /* the reference's strings: "circular", "linear-open-hairpin", ...; NULL beyond AC_TOPOLOGY_OTHER */
 void ac_components_free(ac_components*);
 
+/* The linear-path merge plan: what merge_linear_paths (graph_simplification.rs:315-371) would do to a graph, and the products of doing it —
+ * which unitigs merge into which chains, in which order and on which strand, the new numbers, the merged sequences, depths and types
+ * (merge_path :410-485, get_merge_path_depth :501-526) and the link set after the merge and delete_dangling_links.  Read-only: no handle
+ * is edited; applying the plan to a graph, the positions and P lines of merged unitigs, renumber_unitigs and the GFA stay with the caller.
+ * The link entries among alive unitigs must be a SET that is closed under reverse complement: a duplicated entry, or an entry (a, b)
+ * without (-b, -a), is an error (the first one by index is quoted), because the reference's sequential loop has an order-free form only
+ * then.  The fixed starts and ends are the reference's own (get_fixed_unitig_starts_and_ends :190-230 on the first and last entry of every
+ * path, then fix_circular_loops :374-384).
+ * Chains come in the order the reference finds them — ascending number of the unitig they are found from — and chain i gets the number
+ * n_unitigs + 1 + i (n_unitigs = the highest number, alive or not).  A chain's members are signed numbers in path order.
+ * Everything but the depth and type rules runs on the device; the number of launches grows with log2(n_unitigs) only, never with the
+ * length of a chain.  The host reads one 64-byte header and then the results, sized by it.
+ * Errors (return 1, ac_last_error), never faults: a link that names unitig 0 or one above n_unitigs, a duplicated link, a link whose reverse
+ * complement is missing, a path end that names a dead or nonexistent unitig, unitig_len NULL, only one of seq_bytes and seq_begin, NULL
+ * out, a handle without host arrays.  n_unitigs == 0 is a valid, empty result. */
+typedef struct ac_merge ac_merge;
+typedef struct {
+    uint32_t number;         /* the merged unitig's number: n_unitigs + 1 + index */
+    uint32_t members;        /* >= 2 */
+    uint64_t length;         /* sum of member lengths = bytes of the merged sequence */
+    uint64_t member_off;     /* first member in ac_merge_members */
+    uint64_t seq_off;        /* first byte in ac_merge_sequences (filled whether or not sequences were copied) */
+    double   depth;          /* get_merge_path_depth: the first member's position count on its strand if non-zero, else the first Anchor member's
+                                depth, else sum(depth * len) / sum(len) as one sequential sum in path order */
+    uint8_t  type;           /* AC_UNITIG_CONSENTIG if any member is Anchor or Consentig, else AC_UNITIG_OTHER */
+    uint8_t  loop;           /* the last member links to the first: the merged unitig gets the link + -> + (and - -> -) */
+} ac_merge_chain;
+typedef struct {
+    uint32_t size;           /* the library's sizeof(ac_merge_summary) */
+    uint32_t chains, merged_unitigs, unitigs_after;   /* unitigs_after: alive - merged_unitigs + chains */
+    uint64_t links_after, bases_copied;
+    uint32_t launches, read_backs;
+    double seconds_device;   /* the kernels of the call, by device events (the components pass included) */
+    double seconds_copy;     /* of those, the kernel that copies the merged sequences */
+} ac_merge_summary;
+enum { AC_UNITIG_OTHER, AC_UNITIG_ANCHOR, AC_UNITIG_CONSENTIG, AC_UNITIG_BRIDGE };
+/* On a graph handle (a build, or ac_graph_from_gfa): its links, lengths, depths and sequences; every unitig alive and of type Other.
+ * use_paths = 1: the path ends and the per-strand position counts (a histogram of the signed path entries, taken on the device: what
+ * create_sequence_and_positions yields, unitig_graph.rs:151-174) come from the handle's paths.  use_paths = 0: a call with `seqs` empty on
+ * a graph without positions — everything mergeable merges.  with_sequences = 0: no bytes are copied (seq_off is still filled). */
+int ac_graph_merge_plan(const ac_graph*, int use_paths, int with_sequences, int device, ac_merge** out);
+/* The same on the caller's arrays, for a graph that has been edited.  alive as for ac_components_from_links.  path_ends: the first and
+ * last signed entry of each of n_seqs non-empty paths.  fwd_positions / rev_positions: how many positions each unitig holds per strand. */
+int ac_merge_plan_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len,
+        const uint8_t* alive /* or NULL */, const int32_t* path_ends /* first,last per sequence; or NULL */, uint32_t n_seqs,
+        const double* depth /* or NULL = 0 */, const uint32_t* fwd_positions, const uint32_t* rev_positions /* or NULL = none */,
+        const uint8_t* type /* AC_UNITIG_OTHER/ANCHOR/CONSENTIG/BRIDGE, or NULL */,
+        const uint8_t* seq_bytes, const uint64_t* seq_begin /* both or neither */, int device, ac_merge** out);
+/* The arrays belong to the handle. */
+int ac_merge_chains(const ac_merge*, const ac_merge_chain** chains, uint32_t* n);
+int ac_merge_members(const ac_merge*, const int32_t** members /* signed numbers in path order, chain after chain */, uint64_t* n);
+int ac_merge_chain_of_unitig(const ac_merge*, const uint32_t** chain /* n_unitigs; UINT32_MAX = not merged */);
+int ac_merge_fixed_flags(const ac_merge*, const uint8_t** flags /* n_unitigs; 1 = fixed start, 2 = fixed end, after fix_circular_loops */);
+int ac_merge_sequences(const ac_merge*, const uint8_t** bytes, uint64_t* n /* 0 when no sequences were given or asked for */);
+/* The links after the merge as a SET, ascending by (a, b) as signed numbers — not get_links_for_gfa order. */
+int ac_merge_links(const ac_merge*, const ac_link** links, uint64_t* n);
+size_t ac_merge_summary_get_sized(const ac_merge*, ac_merge_summary* out, size_t out_size);
+void ac_merge_free(ac_merge*);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -830,8 +889,11 @@ const char* ac_version(void);
  *      ac_selftest_arena, ac_selftest_launch, ac_selftest_atomics, ac_selftest_side_order, ac_selftest_event_ring.
  *  12: additions only: ac_graph_components, ac_components_from_links, ac_components_records, ac_components_of_unitig,
  *      ac_components_members, ac_components_unitig_flags, ac_components_summary_get_sized, ac_topology_name, ac_components_free with
- *      ac_component, ac_components_summary and the AC_TOPOLOGY_* values. */
-#define AC_ABI_VERSION 12
+ *      ac_component, ac_components_summary and the AC_TOPOLOGY_* values.
+ *  13: additions only: ac_graph_merge_plan, ac_merge_plan_from_links, ac_merge_chains, ac_merge_members, ac_merge_chain_of_unitig,
+ *      ac_merge_fixed_flags, ac_merge_sequences, ac_merge_links, ac_merge_summary_get_sized, ac_merge_free with ac_merge_chain,
+ *      ac_merge_summary and the AC_UNITIG_* values. */
+#define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
 
