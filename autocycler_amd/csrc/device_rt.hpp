@@ -22,6 +22,15 @@
 #ifndef AC_EMU
 #include <hip/hip_runtime.h>
 #endif
+// The guarded arena (tests only: the emulation under AddressSanitizer, tests/c_client/kernel_bounds_check.cpp).  AC_ARENA_GUARD=1: only the bytes an
+// allocation asked for are addressable, its rounding tail and a red zone behind it are poisoned, fresh and reset blocks are poisoned;
+// AC_ARENA_GUARD=2 (strict): what a rewind releases is poisoned at once as well.  Without the macro nothing below differs from before.
+#if defined(AC_EMU) && defined(AC_ARENA_GUARD)
+#include <sanitizer/asan_interface.h>
+#define AC_GUARD_LEVEL AC_ARENA_GUARD
+#else
+#define AC_GUARD_LEVEL 0
+#endif
 
 namespace ac {
 
@@ -121,9 +130,24 @@ class Arena {
     Arena() : host_(false) {}
     ~Arena() { for (auto& b : blocks_) raw_free(b.p); }
     static const size_t COALESCE_LIMIT = (size_t)16 << 30;
+#if AC_GUARD_LEVEL
+    static const size_t RED_ZONE = 256;      // poisoned bytes behind every allocation's rounded size
+    static void guard_poison(const void* p, size_t n) { if (n) __asan_poison_memory_region(p, n); }
+    static void guard_unpoison(const void* p, size_t n) { if (n) __asan_unpoison_memory_region(p, n); }
+#else
+    static const size_t RED_ZONE = 0;
+    static void guard_poison(const void*, size_t) {}
+    static void guard_unpoison(const void*, size_t) {}
+#endif
+    // A DELIBERATE read of memory that a rewind has released: the caller names the bytes and states, where it calls this, why they still hold
+    // what it reads (DESIGN.md lists every call).  Nothing outside the guard (at level 1 it undoes what the red zone of an allocation made since
+    // the rewind may have poisoned of those bytes).
+    static void keep_readable(const void* p, size_t bytes) { guard_unpoison(p, bytes); }
     void* alloc(size_t bytes) {
+        [[maybe_unused]] const size_t asked = bytes;
         bytes = (bytes + 255) & ~(size_t)255;
         if (bytes == 0) bytes = 256;
+        bytes += RED_ZONE;
         // first fit, forwards only: blocks behind the current one are empty (a rewind emptied them) or do not exist yet
         size_t i = cur_;
         while (i < blocks_.size() && blocks_[i].used + bytes > blocks_[i].cap) i++;
@@ -136,6 +160,7 @@ class Arena {
         void* r = (char*)b.p + b.used;
         b.used += bytes;
         peak_ = std::max(peak_, total_used());
+        guard_poison(r, bytes); guard_unpoison(r, asked);      // (rewound space may still be addressable from its last use)
         return r;
     }
     // Start of a build: everything handed out so far is dead.
@@ -152,7 +177,7 @@ class Arena {
             Block b; b.cap = total; b.used = 0; b.p = raw_alloc(total);
             blocks_.push_back(b);
         } else {   // a large arena keeps its blocks: the next build of the same job makes the same requests in the same order and fits them the same
-            for (auto& b : blocks_) b.used = 0;      // way, and giving 150 GB back and asking for it again costs seconds (configs[4]: 8 s)
+            for (auto& b : blocks_) { b.used = 0; guard_poison(b.p, b.cap); }      // way, and giving 150 GB back and asking for it again costs seconds (configs[4]: 8 s)
         }
     }
     // First build of a process: one block of about the size the build will need, so that neither this build grows the
@@ -178,7 +203,12 @@ class Arena {
         on_rewind();
         if (blocks_.empty()) return;
         cur_ = m.empty ? 0 : m.block;
-        blocks_[cur_].used = m.empty ? 0 : m.used;
+        const size_t keep = m.empty ? 0 : m.used;
+        if (AC_GUARD_LEVEL >= 2) {      // strict: what the rewind releases is poisoned at once (level 1: when it is handed out again, by alloc's rule)
+            if (blocks_[cur_].used > keep) guard_poison((char*)blocks_[cur_].p + keep, blocks_[cur_].used - keep);
+            for (size_t i = cur_ + 1; i < blocks_.size(); i++) guard_poison(blocks_[i].p, blocks_[i].used);
+        }
+        blocks_[cur_].used = keep;
         for (size_t i = cur_ + 1; i < blocks_.size(); i++) blocks_[i].used = 0;      // kept for the allocations to come (no hipFree: it waits for the device)
     }
     size_t peak() const { return peak_; }
@@ -209,6 +239,7 @@ class Arena {
 #ifdef AC_EMU
         void* p = malloc(bytes);
         if (!p) throw DeviceError("emu malloc failed");
+        guard_poison(p, bytes);      // (a fresh block: nothing of it has been handed out)
         return p;
 #else
         void* p = nullptr;
@@ -220,6 +251,7 @@ class Arena {
     void raw_free(void* p) {
         const double t0 = wall();
 #ifdef AC_EMU
+        for (auto& b : blocks_) if (b.p == p) guard_unpoison(b.p, b.cap);      // (the heap takes back plain memory)
         free(p);
 #else
         if (host_) (void)hipHostFree(p); else (void)hipFree(p);
@@ -257,9 +289,14 @@ class PinnedPool {
             size_t cap = bytes + bytes / 8 + 4096;
             if (getenv("AC_DEBUG_ARENA")) fprintf(stderr, "pinned pool: new block of %zu bytes (%zu free entries)\n", cap, free_.size());
 #ifdef AC_EMU
+            [[maybe_unused]] const size_t stated = cap;
             cap = (cap + 4095) & ~(size_t)4095;
             b.p = aligned_alloc(4096, cap);      // (page-aligned like hipHostMalloc's blocks: the streaming stretch writer wants whole 64-byte lines)
             if (!b.p) throw DeviceError("out of host memory");
+#if AC_GUARD_LEVEL
+            Arena::guard_poison((char*)b.p + stated, cap - stated);      // the block is what the device build states (hipHostMalloc gets no rounding): the tail of this
+            cap = stated;                                                // rounding is nobody's (it stays poisoned while the block is pooled; free() takes it as it is)
+#endif
 #else
             AC_HIP_CHECK(hipHostMalloc(&b.p, cap, hipHostMallocDefault));
 #endif

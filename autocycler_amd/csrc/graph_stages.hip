@@ -385,10 +385,14 @@ template <int W> void GraphBuilder::Impl::degrees() {
                 // (nothing but sizes promised that the two do not overlap — F can reach twice the fragment count, AC_DEGREE_REGION_CAP
                 // shrinks the queues — and an overlapping device-to-device copy is undefined: then through a buffer behind both)
                 const u8* dst_b = (const u8*)kcontrib.ptr(); const u8* src_b = (const u8*)kc_src;
-                if (dst_b + kc_bytes <= src_b || src_b + kc_bytes <= dst_b) copy_d2d(kcontrib.ptr(), kc_src, kc_bytes);
+                // kc_src is read AFTER the rewind that released it, on purpose: between the rewind six lines up and the copies below nothing but
+                // kcontrib (and pad and bounce, which lie behind the source's end) is allocated and nothing is launched, an allocation writes nothing,
+                // and the overlap of source and destination is tested right here
+                if (dst_b + kc_bytes <= src_b || src_b + kc_bytes <= dst_b) { Arena::keep_readable(kc_src, kc_bytes); copy_d2d(kcontrib.ptr(), kc_src, kc_bytes); }
                 else {
                     const Arena::Mark bounce_mark = Arena::device().mark();
                     DBuf<u32> pad((u64)(src_b + kc_bytes - dst_b) / 4 + 1), bounce(n_pending + n_first + 1);      // (pad: up to the end of the source, so that the bounce lies behind it)
+                    Arena::keep_readable(kc_src, kc_bytes);
                     copy_d2d(bounce.ptr(), kc_src, kc_bytes);
                     copy_d2d(kcontrib.ptr(), bounce.ptr(), kc_bytes);
                     stream_sync();
@@ -701,9 +705,17 @@ template <int W> void GraphBuilder::Impl::walk() {
     {
         DBuf<int32_t> packed(n_ent);      // (beyond the staging area: the compaction reads rows that later wavefronts' outputs would overwrite)
         launch_full(((n_walkers + 63) / 64) * 64, PathCompactFunctor{stage.ptr(), wcount.ptr(), woff.ptr(), PC, n_walkers, packed.ptr()});
+        const size_t stage_bytes = stage.bytes();
         stage = DBuf<int32_t>(); woff = DBuf<u64>(); seq_tid = DBuf<u32>(); seq_j = DBuf<u32>(); uinfo = DBuf<V16>();
         Arena::device().rewind(walk_mark);
         ent_val.alloc(n_ent);             // where the staging area began; `packed` lies behind the staging area's end (n_ent <= its size)
+        // `packed` is read AFTER the rewind that released it, on purpose.  It still holds the entries because
+        // (1) ent_val is the only allocation since the rewind, (2) ent_val is no larger than the staging area, the first allocation behind the mark,
+        // so it ends before `packed`, the last one, begins, and (3) all of this is stream 0 in order.  Both are checked, not assumed:
+        const char* const ev = (const char*)ent_val.ptr(); const char* const pk = (const char*)packed.ptr();
+        if (n_ent * 4 > stage_bytes || (ev != pk && ev < pk + n_ent * 4 && pk < ev + n_ent * 4))
+            throw DeviceError("path walk: the compacted entries overlap the place they are copied to");
+        Arena::keep_readable(packed.ptr(), n_ent * 4);
         if (ent_val.ptr() != packed.ptr()) copy_d2d(ent_val.ptr(), packed.ptr(), n_ent * 4);
     }
     launch(loc.n_seqs, PathEndsFunctor{ent_val.ptr(), path_off.ptr(), fs0.ptr(), fe0.ptr(), rank.ptr(), uorient.ptr()});

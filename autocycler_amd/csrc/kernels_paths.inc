@@ -577,7 +577,7 @@ struct StretchCountFunctor {
     const int32_t* ent; u64 n; u32* count;      // count[g] for group g = entries [64 g, 64 g + 64); one more group than needed holds 0
     AC_D void operator()(u64 i, bool valid) const {
         const u64 b = wv::ballot(valid && stretch_starts(ent, n, i));
-        if (wv::lane() == 0) count[i >> 6] = (u32)popc64(b);
+        if (valid && wv::lane() == 0) count[i >> 6] = (u32)popc64(b);      // (the launch is whole workgroups: up to three wavefronts lie behind the last group, none of their lanes valid)
     }
 };
 struct StretchRecordFunctor {
