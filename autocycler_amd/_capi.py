@@ -123,6 +123,26 @@ class MergeSummary(C.Structure):      # ac_merge_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class SubsetCluster(C.Structure):      # ac_subset_cluster
+    _fields_ = [("seqs", C.c_uint32), ("unitigs", C.c_uint32), ("entries", C.c_uint64), ("links", C.c_uint64), ("length", C.c_uint64)]
+
+
+class SubsetsSummary(C.Structure):      # ac_subsets_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "clusters", "sequences_kept", "n_unitigs")] + [(n, C.c_uint64) for n in ("entries_kept", "unitigs", "links")] + \
+               [("launches", C.c_uint32), ("read_backs", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
+class MergedPathsSummary(C.Structure):      # ac_merged_paths_summary
+    _fields_ = [("size", C.c_uint32), ("sequences", C.c_uint32), ("entries_before", C.c_uint64), ("entries_after", C.c_uint64),
+                ("launches", C.c_uint32), ("read_backs", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -181,7 +201,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -296,6 +316,28 @@ def load_library(path=None):
     lib.ac_merge_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(MergeSummary), C.c_size_t]
     lib.ac_merge_free.argtypes = [C.c_void_p]
     lib.ac_merge_free.restype = None
+    lib.ac_graph_subsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_subsets_from_paths.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
+                                          C.POINTER(C.c_void_p)]
+    lib.ac_subsets_records.argtypes = [C.c_void_p, C.POINTER(C.POINTER(SubsetCluster)), C.POINTER(C.c_uint32)]
+    lib.ac_subsets_unitigs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
+                                       C.POINTER(C.POINTER(C.c_uint32))]
+    lib.ac_subsets_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(Link))]
+    lib.ac_subsets_seqs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32))]
+    lib.ac_subsets_path_ends.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_int32))]
+    lib.ac_subsets_dense.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ac_subsets_summary_get_sized.restype = C.c_size_t
+    lib.ac_subsets_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(SubsetsSummary), C.c_size_t]
+    lib.ac_subsets_free.argtypes = [C.c_void_p]
+    lib.ac_subsets_free.restype = None
+    lib.ac_subsets_components.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_subsets_merge_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_subsets_merged_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_merged_paths_get.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_int32))]
+    lib.ac_merged_paths_summary_get_sized.restype = C.c_size_t
+    lib.ac_merged_paths_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(MergedPathsSummary), C.c_size_t]
+    lib.ac_merged_paths_free.argtypes = [C.c_void_p]
+    lib.ac_merged_paths_free.restype = None
     lib.ac_cluster_max_seqs.restype = C.c_uint32
     lib.ac_cluster_max_seqs.argtypes = []
     lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -794,8 +836,9 @@ class MergePlan:
     FIXED_START, FIXED_END = 1, 2
     OTHER, ANCHOR, CONSENTIG, BRIDGE = 0, 1, 2, 3
 
-    def __init__(self, lib, h, n_unitigs):
+    def __init__(self, lib, h, n_unitigs, keep=False):
         import numpy as np
+        self._lib, self._h = lib, None      # (keep: the handle lives on for Subsets.merged_paths, until close())
         try:
             dt = np.dtype([("number", "<u4"), ("members", "<u4"), ("length", "<u8"), ("member_off", "<u8"), ("seq_off", "<u8"), ("depth", "<f8"), ("type", "u1"),
                            ("loop", "u1")], align=True)
@@ -825,8 +868,22 @@ class MergePlan:
             sm = MergeSummary()
             assert lib.ac_merge_summary_get_sized(h, C.byref(sm), C.sizeof(MergeSummary)) == C.sizeof(MergeSummary) == sm.size
             self.summary = sm.as_dict()
+            if keep:
+                self._h, h = h, None
         finally:
-            lib.ac_merge_free(h)
+            if h is not None:
+                lib.ac_merge_free(h)
+
+    def close(self):
+        if self._h:
+            self._lib.ac_merge_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def chain_members(self):
         """merge_paths: a list of lists of signed unitig numbers"""
@@ -886,6 +943,200 @@ def merge_plan_from_links(n_unitigs, links, unitig_len, alive=None, path_ends=No
     _check(lib, lib.ac_merge_plan_from_links(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(pe), pe.shape[0], ptr(dp), ptr(fw), ptr(rv), ptr(ty),
                                              ptr(sb), ptr(sg), device, C.byref(h)))
     return MergePlan(lib, h, n_unitigs)
+
+
+class MergedPaths:
+    """What ac_subsets_merged_paths found, copied out of the handle: seq_index (the cluster's kept sequences, ascending), path_off, entries
+    (sequence seq_index[i] = entries[path_off[i] : path_off[i + 1]], merged unitigs under their chain numbers), summary."""
+
+    def __init__(self, lib, h):
+        import numpy as np
+        try:
+            sp, sn, op, ep = C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_int32)()
+            _check(lib, lib.ac_merged_paths_get(h, C.byref(sp), C.byref(sn), C.byref(op), C.byref(ep)))
+            self.seq_index = _take(sp, sn.value, "<u4")
+            self.path_off = _take(op, sn.value + 1, "<u8")
+            self.entries = _take(ep, int(self.path_off[-1]), "<i4")
+            sm = MergedPathsSummary()
+            assert lib.ac_merged_paths_summary_get_sized(h, C.byref(sm), C.sizeof(MergedPathsSummary)) == C.sizeof(MergedPathsSummary) == sm.size
+            self.summary = sm.as_dict()
+        finally:
+            lib.ac_merged_paths_free(h)
+
+    def paths(self):
+        """{sequence index: list of signed numbers}"""
+        off, e = self.path_off.tolist(), self.entries.tolist()
+        return {int(s): e[off[i]:off[i + 1]] for i, s in enumerate(self.seq_index.tolist())}
+
+
+def _take(ptr, n, dtype):
+    import numpy as np
+    dtype = np.dtype(dtype)
+    return np.frombuffer(C.string_at(ptr, n * dtype.itemsize), dtype=dtype) if n else np.zeros(0, dtype=dtype)
+
+
+class Subsets:
+    """Owning handle of an ac_subsets: what every cluster of sequences (1..n_clusters; label 0 = dropped) keeps of a graph.  The arrays are
+    copied out on construction; the handle stays for components / merge_plan / merged_paths until close().
+    records        structured array, one per cluster: seqs, unitigs, entries, links, length
+    unitigs(c)     the alive unitig numbers of cluster c, ascending
+    positions(c)   (fwd_positions, rev_positions) of those unitigs: both the number of kept path entries that name the unitig
+    links(c)       (m, 2) int32: the input's links with both ends alive in c, in the input's order
+    seqs(c)        the kept sequence indices, ascending
+    path_ends(c)   (k, 2) int32: first and last signed entry of every kept sequence with a non-empty path
+    dense(c)       dict alive, fwd_positions, rev_positions, depth: n_unitigs entries each — the arguments of components_from_links /
+                   merge_plan_from_links
+    summary        dict (clusters, sequences_kept, n_unitigs, entries_kept, unitigs, links, launches, read_backs, seconds_device)"""
+
+    def __init__(self, lib, h, n_unitigs, keepalive):
+        import numpy as np
+        self._lib, self._h, self.n_unitigs, self._keepalive = lib, h, n_unitigs, keepalive
+        dt = np.dtype([("seqs", "<u4"), ("unitigs", "<u4"), ("entries", "<u8"), ("links", "<u8"), ("length", "<u8")], align=True)
+        assert dt.itemsize == C.sizeof(SubsetCluster)
+        rp, rn = C.POINTER(SubsetCluster)(), C.c_uint32()
+        _check(lib, lib.ac_subsets_records(h, C.byref(rp), C.byref(rn)))
+        self.n_clusters = nc = rn.value
+        self.records = _take(rp, nc, dt)
+        op, up, fp, vp = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        _check(lib, lib.ac_subsets_unitigs(h, C.byref(op), C.byref(up), C.byref(fp), C.byref(vp)))
+        self.unitig_off = _take(op, nc + 1, "<u8")
+        total = int(self.unitig_off[-1])
+        self._unitigs, self._fwd, self._rev = _take(up, total, "<u4"), _take(fp, total, "<u4"), _take(vp, total, "<u4")
+        op, lp = C.POINTER(C.c_uint64)(), C.POINTER(Link)()
+        _check(lib, lib.ac_subsets_links(h, C.byref(op), C.byref(lp)))
+        self.link_off = _take(op, nc + 1, "<u8")
+        self._links = _take(lp, 2 * int(self.link_off[-1]), "<i4").reshape(-1, 2)
+        op, sp = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+        _check(lib, lib.ac_subsets_seqs(h, C.byref(op), C.byref(sp)))
+        self.seq_off = _take(op, nc + 1, "<u8")
+        self._seqs = _take(sp, int(self.seq_off[-1]), "<u4")
+        op, ep = C.POINTER(C.c_uint64)(), C.POINTER(C.c_int32)()
+        _check(lib, lib.ac_subsets_path_ends(h, C.byref(op), C.byref(ep)))
+        self.ends_off = _take(op, nc + 1, "<u8")
+        self._ends = _take(ep, 2 * int(self.ends_off[-1]), "<i4").reshape(-1, 2)
+        sm = SubsetsSummary()
+        assert lib.ac_subsets_summary_get_sized(h, C.byref(sm), C.sizeof(SubsetsSummary)) == C.sizeof(SubsetsSummary) == sm.size
+        self.summary = sm.as_dict()
+
+    def close(self):
+        if self._h:
+            self._lib.ac_subsets_free(self._h)
+            self._h = None
+        self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _row(self, off, c):
+        if not 1 <= c <= self.n_clusters:
+            raise AutocyclerError(f"cluster {c} does not exist: clusters run from 1 to {self.n_clusters}")
+        return slice(int(off[c - 1]), int(off[c]))
+
+    def unitigs(self, c):
+        return self._unitigs[self._row(self.unitig_off, c)]
+
+    def positions(self, c):
+        r = self._row(self.unitig_off, c)
+        return self._fwd[r], self._rev[r]
+
+    def links(self, c):
+        return self._links[self._row(self.link_off, c)]
+
+    def seqs(self, c):
+        return self._seqs[self._row(self.seq_off, c)]
+
+    def path_ends(self, c):
+        return self._ends[self._row(self.ends_off, c)]
+
+    def dense(self, c):
+        import numpy as np
+        n = self.n_unitigs
+        alive, fwd, rev, depth = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        _check(self._lib, self._lib.ac_subsets_dense(self._h, c, ptr(alive), ptr(fwd), ptr(rev), ptr(depth)))
+        return dict(alive=alive, fwd_positions=fwd, rev_positions=rev, depth=depth)
+
+    def components(self, c, marked=None, device=0):
+        """ac_subsets_components: Components of cluster c's graph"""
+        mk = _bytes_per_unitig(marked, self.n_unitigs, "marked")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_subsets_components(self._h, c, mk.ctypes.data if mk is not None and mk.size else None, device, C.byref(h)))
+        return Components(self._lib, h, self.n_unitigs)
+
+    def merge_plan(self, c, with_sequences=True, sequences=None, device=0):
+        """ac_subsets_merge_plan: the MergePlan of cluster c's graph (its handle stays alive for merged_paths; close() it or let it go).
+        sequences: (all bytes as a uint8 array, the first byte of every unitig as a uint64 array) for an object made from plain arrays."""
+        import numpy as np
+        sb = sg = None
+        if sequences is not None:
+            sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), np.ascontiguousarray(sequences[1], dtype=np.uint64)
+            if sg.shape != (self.n_unitigs,):
+                raise AutocyclerError(f"sequences[1]: one entry per unitig expected ({self.n_unitigs}), got shape {sg.shape}")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_subsets_merge_plan(self._h, c, sb.ctypes.data if sb is not None else None, sg.ctypes.data if sg is not None else None,
+                                                          int(bool(with_sequences)), device, C.byref(h)))
+        return MergePlan(self._lib, h, self.n_unitigs, keep=True)
+
+    def merged_paths(self, c, plan, device=0):
+        """ac_subsets_merged_paths: the paths of cluster c's sequences over the merged unitigs of `plan` (from merge_plan(c))"""
+        if getattr(plan, "_h", None) is None:
+            raise AutocyclerError("merged_paths: the plan must come from Subsets.merge_plan and still be open")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_subsets_merged_paths(self._h, c, plan._h, device, C.byref(h)))
+        return MergedPaths(self._lib, h)
+
+
+def graph_subsets(graph, cluster_of_seq, n_clusters=None, device=0, lib_path=None):
+    """ac_graph_subsets: what every cluster keeps of a Graph's unitigs, links and paths.  cluster_of_seq: one label per sequence in path
+    order, 0 = dropped; n_clusters: None = the highest label (at least 1).  The Subsets keeps the graph alive."""
+    import numpy as np
+    lib = graph._lib
+    labels = np.ascontiguousarray(np.asarray(cluster_of_seq, dtype=np.uint16))
+    n_seqs = lib.ac_graph_seq_count(graph._h)
+    if labels.shape != (n_seqs,):
+        raise AutocyclerError(f"cluster_of_seq: one label per sequence expected ({n_seqs}), got shape {labels.shape}")
+    if n_clusters is None:
+        n_clusters = max(1, int(labels.max())) if labels.size else 1
+    h = C.c_void_p()
+    _check(lib, lib.ac_graph_subsets(graph._h, labels.ctypes.data if labels.size else None, n_clusters, device, C.byref(h)))
+    return Subsets(lib, h, graph.unitig_count, (graph,))
+
+
+def subsets_from_paths(n_unitigs, links, unitig_len, paths, cluster_of_seq, n_clusters=None, alive=None, device=0, lib_path=None):
+    """ac_subsets_from_paths: the same on plain arrays.  links: (a, b) pairs of signed unitig numbers in L-line order; paths: a list of lists
+    of signed numbers, or a tuple (entries as an int32 array, offsets as a uint64 array of n_seqs + 1); alive: the unitigs that are still
+    there (None = all)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+    ln = np.ascontiguousarray(np.asarray(unitig_len, dtype=np.uint32))
+    if ln.shape != (n_unitigs,):
+        raise AutocyclerError(f"unitig_len: one entry per unitig expected ({n_unitigs}), got shape {ln.shape}")
+    al = _bytes_per_unitig(alive, n_unitigs, "alive")
+    if isinstance(paths, tuple):
+        ent, off = np.ascontiguousarray(paths[0], dtype=np.int32), np.ascontiguousarray(paths[1], dtype=np.uint64)
+    else:
+        ent = np.ascontiguousarray(np.fromiter((e for p in paths for e in p), dtype=np.int32))
+        off = np.zeros(len(paths) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64) if len(paths) else []
+    n_seqs = off.shape[0] - 1
+    labels = np.ascontiguousarray(np.asarray(cluster_of_seq, dtype=np.uint16))
+    if labels.shape != (n_seqs,):
+        raise AutocyclerError(f"cluster_of_seq: one label per sequence expected ({n_seqs}), got shape {labels.shape}")
+    if n_clusters is None:
+        n_clusters = max(1, int(labels.max())) if labels.size else 1
+    if ln.size == 0:
+        ln = np.zeros(1, dtype=np.uint32)      # (n_unitigs == 0: the entry still wants a pointer)
+    if labels.size == 0:
+        labels = np.zeros(1, dtype=np.uint16)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_subsets_from_paths(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(ent), off.ctypes.data, n_seqs, ptr(labels), n_clusters, device,
+                                          C.byref(h)))
+    return Subsets(lib, h, n_unitigs, (la, ln, ent, off))
 
 
 class ClusterTree:

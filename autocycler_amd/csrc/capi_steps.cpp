@@ -316,6 +316,7 @@ void ac_components_free(ac_components* c) { delete c; }
 struct ac_merge {
     MergeResult r;
     ac_merge_summary summary;
+    uint32_t cluster = 0;      // made by ac_subsets_merge_plan: for which cluster (ac_subsets_merged_paths checks it); 0: by another entry
 };
 static_assert(sizeof(ac_merge_chain) == sizeof(MergeChainRecord) && offsetof(ac_merge_chain, length) == offsetof(MergeChainRecord, length) &&
               offsetof(ac_merge_chain, seq_off) == offsetof(MergeChainRecord, seq_off) && offsetof(ac_merge_chain, depth) == offsetof(MergeChainRecord, depth) &&
@@ -425,6 +426,195 @@ size_t ac_merge_summary_get_sized(const ac_merge* m, ac_merge_summary* out, size
     return sizeof(ac_merge_summary);
 }
 void ac_merge_free(ac_merge* m) { delete m; }
+
+// ---- sequence subsets: what every cluster of sequences keeps of a graph, and one cluster's paths over the merged unitigs of its plan, on the
+// device (kernels_subset.inc); labels, sequence lists, path ends and the densified arrays on the host (subset_host.cpp).  Read-only ----
+struct ac_subsets {
+    SubsetResult r;
+    SubsetPlan plan;
+    ac_subsets_summary summary;
+    // borrowed from the caller until ac_subsets_free
+    const ac_link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const int32_t* path = nullptr; const uint64_t* path_off = nullptr;
+    const ac_graph* graph = nullptr;
+};
+struct ac_merged_paths {
+    MergedPathsResult r;
+    ac_merged_paths_summary summary;
+};
+static_assert(sizeof(ac_subset_cluster) == sizeof(SubsetClusterRecord) && offsetof(ac_subset_cluster, entries) == offsetof(SubsetClusterRecord, entries) &&
+              offsetof(ac_subset_cluster, length) == offsetof(SubsetClusterRecord, length), "ac_subset_cluster and SubsetClusterRecord are one layout");
+static_assert(sizeof(ac_link) == sizeof(SubsetLink), "ac_link and SubsetLink are one layout");
+static void subsets_run(uint32_t n, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path, const uint64_t* path_off,
+                        uint32_t n_seqs, const uint16_t* cluster_of_seq, uint32_t n_clusters, const ac_graph* graph, int device, ac_subsets** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!cluster_of_seq) throw DeviceError("null pointer: cluster_of_seq");
+    if (!path_off) throw DeviceError("null pointer: path_off");
+    if (!unitig_len) throw DeviceError("null pointer: unitig_len");
+    if (n_links && !links) throw DeviceError("null pointer: n_links > 0 without links");
+    auto h = std::make_unique<ac_subsets>();
+    h->links = links; h->n_links = n_links; h->unitig_len = unitig_len; h->path = path; h->path_off = path_off; h->graph = graph;
+    h->r.n_unitigs = n;
+    subset_prepare(n_seqs, path, path_off, cluster_of_seq, n_clusters, &h->plan, &h->r);
+    if (n == 0 || h->plan.kept_entries() == 0) {      // (nothing is alive anywhere; no device is asked for)
+        if (h->plan.kept_entries()) {
+            uint32_t seq = 0; uint64_t index = 0;
+            subset_locate(h->plan, 0, &seq, &index);
+            throw DeviceError(subset_bad_entry_message(seq, index, path[path_off[seq] + index], n));
+        }
+        if (n == 0 && n_links) throw DeviceError(components_bad_link_message(0, links[0].a, links[0].b, 0));
+        subset_empty_products(&h->r);
+    } else {
+        SubsetInput in;
+        in.n_unitigs = n; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.alive = alive; in.path = path; in.path_off = path_off;
+        in.n_clusters = n_clusters; in.plan = &h->plan;
+        DeviceCall call(device);
+        subsets_device(in, &h->r);
+    }
+    subset_finish(&h->r, h->plan);
+    ac_subsets_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.clusters = n_clusters; sm.sequences_kept = (uint32_t)h->plan.kept_seq.size(); sm.n_unitigs = n;
+    sm.entries_kept = h->r.kept_entries; sm.unitigs = h->r.unitigs.size(); sm.links = h->r.links.size();
+    sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+    *out = h.release();
+}
+int ac_subsets_from_paths(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path_entries,
+                          const uint64_t* path_off, uint32_t n_seqs, const uint16_t* cluster_of_seq, uint32_t n_clusters, int device, ac_subsets** out) {
+    return guarded([&] { subsets_run(n_unitigs, links, n_links, unitig_len, alive, path_entries, path_off, n_seqs, cluster_of_seq, n_clusters, nullptr, device, out); });
+}
+int ac_graph_subsets(const ac_graph* g, const uint16_t* cluster_of_seq, uint32_t n_clusters, int device, ac_subsets** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!g) throw DeviceError("null pointer");
+        if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+        const FinalGraph& f = g->g;
+        const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+        if (f.path_off.size() != (size_t)n_seqs + 1) throw DeviceError("subsets: the graph holds no paths");
+        subsets_run(f.n_unitigs, (const ac_link*)f.links, f.n_links, f.seq_len, nullptr, f.path, f.path_off.data(), n_seqs, cluster_of_seq, n_clusters, g, device, out);
+    });
+}
+int ac_subsets_records(const ac_subsets* s, const ac_subset_cluster** records, uint32_t* n_clusters) {
+    return guarded([&] {
+        if (!s || !records || !n_clusters) throw DeviceError("null pointer");
+        *records = (const ac_subset_cluster*)s->r.records.data(); *n_clusters = s->r.n_clusters;
+    });
+}
+int ac_subsets_unitigs(const ac_subsets* s, const uint64_t** off, const uint32_t** unitigs, const uint32_t** fwd_positions, const uint32_t** rev_positions) {
+    return guarded([&] {
+        if (!s || !off || !unitigs) throw DeviceError("null pointer");
+        *off = s->r.unitig_off.data(); *unitigs = s->r.unitigs.data();
+        if (fwd_positions) *fwd_positions = s->r.positions.data();
+        if (rev_positions) *rev_positions = s->r.positions.data();
+    });
+}
+int ac_subsets_links(const ac_subsets* s, const uint64_t** off, const ac_link** links) {
+    return guarded([&] {
+        if (!s || !off || !links) throw DeviceError("null pointer");
+        *off = s->r.link_off.data(); *links = (const ac_link*)s->r.links.data();
+    });
+}
+int ac_subsets_seqs(const ac_subsets* s, const uint64_t** off, const uint32_t** seq_index) {
+    return guarded([&] {
+        if (!s || !off || !seq_index) throw DeviceError("null pointer");
+        *off = s->r.seq_off.data(); *seq_index = s->r.seq_index.data();
+    });
+}
+int ac_subsets_path_ends(const ac_subsets* s, const uint64_t** off, const int32_t** path_ends) {
+    return guarded([&] {
+        if (!s || !off || !path_ends) throw DeviceError("null pointer");
+        *off = s->r.ends_off.data(); *path_ends = s->r.path_ends.data();
+    });
+}
+int ac_subsets_dense(const ac_subsets* s, uint32_t cluster, uint8_t* alive, uint32_t* fwd_positions, uint32_t* rev_positions, double* depth) {
+    return guarded([&] {
+        if (!s) throw DeviceError("null pointer");
+        subset_dense(s->r, cluster, alive, fwd_positions, rev_positions, depth);
+    });
+}
+size_t ac_subsets_summary_get_sized(const ac_subsets* s, ac_subsets_summary* out, size_t out_size) {
+    if (s && out) memcpy(out, &s->summary, std::min(out_size, sizeof(ac_subsets_summary)));
+    return sizeof(ac_subsets_summary);
+}
+void ac_subsets_free(ac_subsets* s) { delete s; }
+
+int ac_subsets_components(const ac_subsets* s, uint32_t cluster, const uint8_t* marked, int device, ac_components** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!s) throw DeviceError("null pointer");
+        const uint32_t n = s->r.n_unitigs;
+        std::vector<uint8_t> alive(n);
+        subset_dense(s->r, cluster, alive.data(), nullptr, nullptr, nullptr);
+        const uint64_t l0 = s->r.link_off[cluster - 1], l1 = s->r.link_off[cluster];
+        components_run(n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), marked, device, out);
+    });
+}
+int ac_subsets_merge_plan(const ac_subsets* s, uint32_t cluster, const uint8_t* seq_bytes, const uint64_t* seq_begin, int with_sequences, int device, ac_merge** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!s) throw DeviceError("null pointer");
+        if ((seq_bytes == nullptr) != (seq_begin == nullptr)) throw DeviceError("seq_bytes and seq_begin: both or neither");
+        const uint32_t n = s->r.n_unitigs;
+        std::vector<uint8_t> alive(n);
+        std::vector<uint32_t> positions(n);
+        std::vector<double> depth(n);
+        subset_dense(s->r, cluster, alive.data(), positions.data(), nullptr, depth.data());
+        uint64_t seq_total = 0;
+        if (!with_sequences) { seq_bytes = nullptr; seq_begin = nullptr; }
+        else if (!seq_bytes && s->graph && s->graph->g.seq_block.p && s->graph->g.seq_begin) {
+            seq_bytes = (const uint8_t*)s->graph->g.seq_block.p; seq_begin = s->graph->g.seq_begin; seq_total = s->graph->g.seq_block.bytes;
+        } else if (seq_bytes)
+            for (uint32_t u = 0; u < n; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + s->unitig_len[u]);
+        const uint64_t l0 = s->r.link_off[cluster - 1], l1 = s->r.link_off[cluster], e0 = s->r.ends_off[cluster - 1], e1 = s->r.ends_off[cluster];
+        merge_run(n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), s->r.path_ends.data() + 2 * e0, (uint32_t)(e1 - e0), depth.data(),
+                  positions.data(), positions.data(), nullptr, seq_bytes, seq_begin, seq_total, nullptr, 0, device, out);
+        (*out)->cluster = cluster;
+    });
+}
+int ac_subsets_merged_paths(const ac_subsets* s, uint32_t cluster, const ac_merge* plan, int device, ac_merged_paths** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!s || !plan) throw DeviceError("null pointer");
+        subset_check_cluster(s->r, cluster);
+        if (plan->r.n_unitigs != s->r.n_unitigs)
+            throw DeviceError("merged paths: the plan is over " + std::to_string(plan->r.n_unitigs) + " unitigs, the subsets over " + std::to_string(s->r.n_unitigs));
+        if (plan->cluster == 0) throw DeviceError("merged paths: the plan was not made by ac_subsets_merge_plan");
+        if (plan->cluster != cluster)
+            throw DeviceError("merged paths: the plan was made for cluster " + std::to_string(plan->cluster) + ", not for cluster " + std::to_string(cluster));
+        auto h = std::make_unique<ac_merged_paths>();
+        const size_t first = (size_t)s->r.seq_off[cluster - 1], count = (size_t)(s->r.seq_off[cluster] - s->r.seq_off[cluster - 1]);
+        h->r.seq_index.assign(s->r.seq_index.begin() + first, s->r.seq_index.begin() + first + count);
+        if (s->plan.kept_off[first + count] == s->plan.kept_off[first]) {      // (no entry: nothing to launch)
+            h->r.path_off.assign(count + 1, 0);
+        } else {
+            MergedPathsInput in;
+            in.n_unitigs = s->r.n_unitigs; in.unitig_len = s->unitig_len; in.path = s->path; in.path_off = s->path_off; in.plan = &s->plan; in.kept_first = first;
+            in.kept_count = count; in.merge = &plan->r;
+            DeviceCall call(device);
+            merged_paths_device(in, &h->r);
+        }
+        ac_merged_paths_summary& sm = h->summary;
+        memset(&sm, 0, sizeof sm);
+        sm.size = (uint32_t)sizeof sm; sm.sequences = (uint32_t)count; sm.entries_before = h->r.entries_before; sm.entries_after = h->r.entries.size();
+        sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+        *out = h.release();
+    });
+}
+int ac_merged_paths_get(const ac_merged_paths* p, const uint32_t** seq_index, uint32_t* n_seqs, const uint64_t** path_off, const int32_t** entries) {
+    return guarded([&] {
+        if (!p || !seq_index || !n_seqs || !path_off || !entries) throw DeviceError("null pointer");
+        *seq_index = p->r.seq_index.data(); *n_seqs = (uint32_t)p->r.seq_index.size(); *path_off = p->r.path_off.data(); *entries = p->r.entries.data();
+    });
+}
+size_t ac_merged_paths_summary_get_sized(const ac_merged_paths* p, ac_merged_paths_summary* out, size_t out_size) {
+    if (p && out) memcpy(out, &p->summary, std::min(out_size, sizeof(ac_merged_paths_summary)));
+    return sizeof(ac_merged_paths_summary);
+}
+void ac_merged_paths_free(ac_merged_paths* p) { delete p; }
 
 // ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
 // from it on the host (cluster_host.cpp); the QC verdicts, scores and refinement further down.  Writing the clusters stays with the caller ----

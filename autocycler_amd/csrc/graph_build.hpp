@@ -16,6 +16,7 @@
 #include "resolve_host.hpp"
 #include "components_host.hpp"
 #include "merge_host.hpp"
+#include "subset_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -227,6 +228,21 @@ struct MergePlanInput {
     const uint8_t* seq_bytes = nullptr; const uint64_t* seq_begin = nullptr; uint64_t seq_total = 0;
 };
 void merge_plan_device(const MergePlanInput& in, MergeResult* out);
+// Sequence subsets (kernels_subset.inc): per cluster of sequences the unitigs its paths visit with their position counts, and the links whose
+// two ends it keeps, in the input's order.  plan: subset_prepare's; the entries of the kept sequences are uploaded cluster after cluster.
+// Fills unitig_off, unitigs, positions, length_at, link_off and links of `out`; the rest is subset_host.cpp's.
+struct SubsetInput {
+    uint32_t n_unitigs = 0; const Link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const uint8_t* alive = nullptr;
+    const int32_t* path = nullptr; const uint64_t* path_off = nullptr; uint32_t n_clusters = 0; const SubsetPlan* plan = nullptr;
+};
+void subsets_device(const SubsetInput& in, SubsetResult* out);
+// The paths of one cluster's kept sequences over the merged unitigs of a plan (kernels_subset.inc): every traversal of a chain becomes the
+// chain's signed number.  kept_first / kept_count: the cluster's range of plan.kept_seq.
+struct MergedPathsInput {
+    uint32_t n_unitigs = 0; const uint32_t* unitig_len = nullptr; const int32_t* path = nullptr; const uint64_t* path_off = nullptr;
+    const SubsetPlan* plan = nullptr; size_t kept_first = 0, kept_count = 0; const MergeResult* merge = nullptr;
+};
+void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

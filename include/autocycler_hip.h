@@ -593,6 +593,95 @@ int ac_merge_links(const ac_merge*, const ac_link** links, uint64_t* n);
 size_t ac_merge_summary_get_sized(const ac_merge*, ac_merge_summary* out, size_t out_size);
 void ac_merge_free(ac_merge*);
 
+/* Sequence subsets: what every cluster of sequences keeps of a graph — the edit that save_cluster_gfa (cluster.rs:794-806), clean_up_graph
+ * (trim.rs:260-269) and resolve.rs:248 make before merge_linear_paths: drop the other sequences, recount the positions, remove the unitigs
+ * nobody visits any more (remove_zero_depth_unitigs, unitig_graph.rs:582-586) and their links (delete_dangling_links :547-564) — for all
+ * clusters in one call.  Read-only and on plain arrays: no handle is edited and none is made; the results feed ac_components_from_links and
+ * ac_merge_plan_from_links directly (ac_subsets_dense, or the two composed entries below).  renumber_unitigs and the GFA text stay with the
+ * caller.
+ * cluster_of_seq: one label per sequence in path order, 0 = dropped, 1..n_clusters — the form ac_cluster_assign and
+ * ac_cluster_qc_assignment return.  Everything comes in compressed-row form, clusters 1..n_clusters in order:
+ *   unitigs     the alive unitigs of the cluster, ascending, with their position counts.  create_sequence_and_positions (:151-174) walks a path
+ *               forwards and its reverse backwards, so an entry on either strand adds one position to the unitig's forward list and one to its
+ *               reverse list: fwd_positions and rev_positions are both the number of entries of the kept paths that name the unitig (the two
+ *               pointers name the same array).  A unitig is alive in the cluster iff that number is above 0 (depth = forward_positions.len())
+ *   links       the input's links whose two unitigs are both alive in the cluster, in the input's order
+ *   seqs        the kept sequences, ascending
+ *   path_ends   first and last signed entry of every kept sequence with a non-empty path, in that order: ac_merge_plan_from_links' path_ends
+ * Everything that grows with the path entries or the links runs on the device: a radix sort of one key per kept entry and a run-length pass
+ * (no atomic per entry), one row of cluster bits per unitig for the links.  The host does what grows with n_seqs alone (labels, sequence
+ * lists, path ends).  The number of launches follows the bit widths of the sort keys only — not n_clusters, n_seqs or how the labels are
+ * spread; the host reads one fixed-size header and then the results, sized by it: two read-backs for 1 cluster as for 300.
+ * Working memory on the device: about 72 bytes per kept path entry (keys, sort buffers, run-length arrays), 24 per link, 32 per kept link
+ * over all clusters, 5 per unitig, and ceil(n_clusters / 64) * 8 bytes per unitig (one bit per cluster and unitig); never a counter per
+ * cluster and unitig.  Fewer than 2^32 - 16 kept entries, links, and kept links over all clusters; sums of unitig lengths below 2^46.
+ * Lifetime: the object BORROWS the arrays it was made from (links, unitig_len, path_entries, path_off; for ac_graph_subsets the handle) — they
+ * must stay valid and unchanged until ac_subsets_free; a handle-made object must be freed before ac_free of its graph.
+ * Errors (return 1, ac_last_error), never faults: a label above n_clusters; n_clusters 0 or above 65535; an entry of a kept path that names
+ * unitig 0 or one above n_unitigs, or enters a unitig that is not alive in the input (the first such entry is quoted); a link that names no
+ * unitig; path_off that decreases; NULL cluster_of_seq, path_off, out or unitig_len; a handle without host arrays or paths.  Valid results,
+ * not errors: a cluster without sequences, a sequence with an empty path, every label 0, n_unitigs == 0. */
+typedef struct ac_subsets ac_subsets;
+typedef struct ac_merged_paths ac_merged_paths;
+typedef struct {
+    uint32_t seqs;           /* kept sequences */
+    uint32_t unitigs;        /* alive unitigs */
+    uint64_t entries;        /* path entries of the kept sequences */
+    uint64_t links;          /* kept links */
+    uint64_t length;         /* total length of the alive unitigs */
+} ac_subset_cluster;
+typedef struct {
+    uint32_t size;           /* the library's sizeof(ac_subsets_summary) */
+    uint32_t clusters, sequences_kept, n_unitigs;
+    uint64_t entries_kept, unitigs, links;   /* sums over the clusters */
+    uint32_t launches, read_backs;
+    double seconds_device;   /* the kernels of the call, by device events */
+} ac_subsets_summary;
+/* On a graph handle (a build, or ac_graph_from_gfa): its links (get_links_for_gfa order), lengths and paths. */
+int ac_graph_subsets(const ac_graph*, const uint16_t* cluster_of_seq /* ac_graph_seq_count() labels */, uint32_t n_clusters, int device, ac_subsets** out);
+/* The same on the caller's arrays, for an edited graph or edited paths (the slices of ac_trim_path_slices).  alive as for
+ * ac_components_from_links. */
+int ac_subsets_from_paths(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive /* or NULL */,
+                          const int32_t* path_entries, const uint64_t* path_off /* n_seqs + 1 */, uint32_t n_seqs, const uint16_t* cluster_of_seq,
+                          uint32_t n_clusters, int device, ac_subsets** out);
+/* The arrays belong to the object; every `off` has n_clusters + 1 entries, cluster c (1-based) = [off[c - 1], off[c]). */
+int ac_subsets_records(const ac_subsets*, const ac_subset_cluster** records, uint32_t* n_clusters);
+int ac_subsets_unitigs(const ac_subsets*, const uint64_t** off, const uint32_t** unitigs, const uint32_t** fwd_positions, const uint32_t** rev_positions);
+int ac_subsets_links(const ac_subsets*, const uint64_t** off, const ac_link** links);
+int ac_subsets_seqs(const ac_subsets*, const uint64_t** off, const uint32_t** seq_index);
+int ac_subsets_path_ends(const ac_subsets*, const uint64_t** off /* in (first, last) pairs */, const int32_t** path_ends);
+/* One cluster as the argument arrays of ac_components_from_links / ac_merge_plan_from_links: n_unitigs entries each, allocated by the
+ * caller, any may be NULL.  depth = fwd_positions as a double (recalculate_depth, unitig.rs:260-262). */
+int ac_subsets_dense(const ac_subsets*, uint32_t cluster, uint8_t* alive, uint32_t* fwd_positions, uint32_t* rev_positions, double* depth);
+size_t ac_subsets_summary_get_sized(const ac_subsets*, ac_subsets_summary* out, size_t out_size);
+void ac_subsets_free(ac_subsets*);
+/* ac_components_from_links / ac_merge_plan_from_links on cluster c: its kept links, alive mask, path ends and position counts, depth =
+ * fwd_positions, every type Other — save_cluster_gfa's graph at the point it calls merge_linear_paths.  seq_bytes / seq_begin: both or
+ * neither, as for ac_merge_plan_from_links; NULL, NULL on a handle-made object takes the handle's sequences.  with_sequences = 0: none. */
+int ac_subsets_components(const ac_subsets*, uint32_t cluster, const uint8_t* marked /* or NULL */, int device, ac_components** out);
+int ac_subsets_merge_plan(const ac_subsets*, uint32_t cluster, const uint8_t* seq_bytes, const uint64_t* seq_begin, int with_sequences, int device,
+                          ac_merge** out);
+/* The P lines after the merge: the path of every kept sequence of the cluster with every traversal of a chain replaced by the chain's number,
+ * + where the path runs through the members in chain order on their chain strands, - where it runs through them backwards on the opposite
+ * strands (a merged loop walked several times: once per lap).  This is what get_unitig_path_for_sequence (unitig_graph.rs:407-465) walks after
+ * merge_path (graph_simplification.rs:414-415): members inside a chain have one way in and one way out and path ends are fixed, so a path
+ * that touches a chain runs through all of it.  plan: from ac_subsets_merge_plan of the same cluster.  Three kernels and three scans
+ * whatever the paths; for every sequence the unitig lengths along the new path must add up to those along the old one (checked on the device).
+ * Errors: a plan of another cluster or another n_unitigs, or one that ac_subsets_merge_plan did not make; a kept path that begins or ends strictly inside a chain, or whose length
+ * changes (the sequence is named) — only a plan that was not made from these paths can do either. */
+typedef struct {
+    uint32_t size;           /* the library's sizeof(ac_merged_paths_summary) */
+    uint32_t sequences;
+    uint64_t entries_before, entries_after;
+    uint32_t launches, read_backs;
+    double seconds_device;
+} ac_merged_paths_summary;
+int ac_subsets_merged_paths(const ac_subsets*, uint32_t cluster, const ac_merge* plan, int device, ac_merged_paths** out);
+int ac_merged_paths_get(const ac_merged_paths*, const uint32_t** seq_index, uint32_t* n_seqs, const uint64_t** path_off /* n_seqs + 1 */,
+                        const int32_t** entries);
+size_t ac_merged_paths_summary_get_sized(const ac_merged_paths*, ac_merged_paths_summary* out, size_t out_size);
+void ac_merged_paths_free(ac_merged_paths*);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -892,7 +981,11 @@ const char* ac_version(void);
  *      ac_component, ac_components_summary and the AC_TOPOLOGY_* values.
  *  13: additions only: ac_graph_merge_plan, ac_merge_plan_from_links, ac_merge_chains, ac_merge_members, ac_merge_chain_of_unitig,
  *      ac_merge_fixed_flags, ac_merge_sequences, ac_merge_links, ac_merge_summary_get_sized, ac_merge_free with ac_merge_chain,
- *      ac_merge_summary and the AC_UNITIG_* values. */
+ *      ac_merge_summary and the AC_UNITIG_* values.  Later additions of the same generation (a caller that does not use them runs
+ *      unchanged): ac_graph_subsets, ac_subsets_from_paths, ac_subsets_records, ac_subsets_unitigs, ac_subsets_links, ac_subsets_seqs,
+ *      ac_subsets_path_ends, ac_subsets_dense, ac_subsets_summary_get_sized, ac_subsets_free, ac_subsets_components, ac_subsets_merge_plan,
+ *      ac_subsets_merged_paths, ac_merged_paths_get, ac_merged_paths_summary_get_sized, ac_merged_paths_free with ac_subset_cluster,
+ *      ac_subsets_summary and ac_merged_paths_summary. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
