@@ -264,7 +264,7 @@ static void components_run(uint32_t n_unitigs, const ac_link* links, uint64_t n_
     memset(&sm, 0, sizeof sm);
     sm.size = (uint32_t)sizeof sm; sm.unitigs = h->r.alive; sm.components = (uint32_t)h->r.records.size(); sm.topology = h->r.topology;
     sm.links_all = h->r.links_all; sm.links_one_way = h->r.links_one_way; sm.total_length = h->r.total_length;
-    sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+    sm.launches = h->r.stats.launches; sm.read_backs = h->r.stats.read_backs; sm.seconds_device = h->r.stats.seconds_device;
     *out = h.release();
 }
 int ac_components_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
@@ -322,7 +322,6 @@ static_assert(sizeof(ac_merge_chain) == sizeof(MergeChainRecord) && offsetof(ac_
               offsetof(ac_merge_chain, seq_off) == offsetof(MergeChainRecord, seq_off) && offsetof(ac_merge_chain, depth) == offsetof(MergeChainRecord, depth) &&
               offsetof(ac_merge_chain, type) == offsetof(MergeChainRecord, type) && offsetof(ac_merge_chain, loop) == offsetof(MergeChainRecord, loop),
               "ac_merge_chain and MergeChainRecord are one layout");
-static_assert(sizeof(ac_link) == sizeof(MergeLink), "ac_link and MergeLink are one layout");
 static_assert((int)AC_UNITIG_OTHER == (int)MERGE_TYPE_OTHER && (int)AC_UNITIG_ANCHOR == (int)MERGE_TYPE_ANCHOR &&
               (int)AC_UNITIG_CONSENTIG == (int)MERGE_TYPE_CONSENTIG && (int)AC_UNITIG_BRIDGE == (int)MERGE_TYPE_BRIDGE, "the AC_UNITIG_* values are merge_host.hpp's");
 // path: the signed entries whose histogram gives the position counts (a handle with use_paths), or null: fwd / rev are the caller's
@@ -353,8 +352,8 @@ static void merge_run(uint32_t n, const ac_link* links, uint64_t n_links, const 
     ac_merge_summary& sm = h->summary;
     memset(&sm, 0, sizeof sm);
     sm.size = (uint32_t)sizeof sm; sm.chains = (uint32_t)h->r.chains.size(); sm.merged_unitigs = h->r.merged_unitigs; sm.unitigs_after = h->r.unitigs_after;
-    sm.links_after = h->r.links.size(); sm.bases_copied = h->r.bases_copied; sm.launches = h->r.launches; sm.read_backs = h->r.read_backs;
-    sm.seconds_device = h->r.seconds_device; sm.seconds_copy = h->r.seconds_copy;
+    sm.links_after = h->r.links.size(); sm.bases_copied = h->r.bases_copied; sm.launches = h->r.stats.launches; sm.read_backs = h->r.stats.read_backs;
+    sm.seconds_device = h->r.stats.seconds_device; sm.seconds_copy = h->r.seconds_copy;
     *out = h.release();
 }
 int ac_merge_plan_from_links(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path_ends,
@@ -443,7 +442,6 @@ struct ac_merged_paths {
 };
 static_assert(sizeof(ac_subset_cluster) == sizeof(SubsetClusterRecord) && offsetof(ac_subset_cluster, entries) == offsetof(SubsetClusterRecord, entries) &&
               offsetof(ac_subset_cluster, length) == offsetof(SubsetClusterRecord, length), "ac_subset_cluster and SubsetClusterRecord are one layout");
-static_assert(sizeof(ac_link) == sizeof(SubsetLink), "ac_link and SubsetLink are one layout");
 static void subsets_run(uint32_t n, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path, const uint64_t* path_off,
                         uint32_t n_seqs, const uint16_t* cluster_of_seq, uint32_t n_clusters, const ac_graph* graph, int device, ac_subsets** out) {
     if (!out) throw DeviceError("null pointer: out");
@@ -476,7 +474,7 @@ static void subsets_run(uint32_t n, const ac_link* links, uint64_t n_links, cons
     memset(&sm, 0, sizeof sm);
     sm.size = (uint32_t)sizeof sm; sm.clusters = n_clusters; sm.sequences_kept = (uint32_t)h->plan.kept_seq.size(); sm.n_unitigs = n;
     sm.entries_kept = h->r.kept_entries; sm.unitigs = h->r.unitigs.size(); sm.links = h->r.links.size();
-    sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+    sm.launches = h->r.stats.launches; sm.read_backs = h->r.stats.read_backs; sm.seconds_device = h->r.stats.seconds_device;
     *out = h.release();
 }
 int ac_subsets_from_paths(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const int32_t* path_entries,
@@ -600,7 +598,7 @@ int ac_subsets_merged_paths(const ac_subsets* s, uint32_t cluster, const ac_merg
         ac_merged_paths_summary& sm = h->summary;
         memset(&sm, 0, sizeof sm);
         sm.size = (uint32_t)sizeof sm; sm.sequences = (uint32_t)count; sm.entries_before = h->r.entries_before; sm.entries_after = h->r.entries.size();
-        sm.launches = h->r.launches; sm.read_backs = h->r.read_backs; sm.seconds_device = h->r.seconds_device;
+        sm.launches = h->r.stats.launches; sm.read_backs = h->r.stats.read_backs; sm.seconds_device = h->r.stats.seconds_device;
         *out = h.release();
     });
 }

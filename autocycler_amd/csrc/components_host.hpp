@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "graph_types.hpp"
+
 namespace ac {
 
 // ac_component, field for field (the device writes these records; capi_steps.cpp asserts the two layouts agree)
@@ -30,9 +32,7 @@ struct ComponentsResult {
     // filled by components_finish
     uint32_t alive = 0, topology = TOPO_EMPTY;
     uint64_t links_all = 0, links_one_way = 0, total_length = 0;
-    // filled by the device driver
-    uint32_t launches = 0, read_backs = 0;
-    double seconds_device = 0;
+    StepStats stats;                          // filled by the device driver
 };
 
 // topology() (unitig_graph.rs:527-545) from the number of alive unitigs, link_count().0 of the graph and, when exactly one unitig is

@@ -86,7 +86,9 @@ __device__ inline u32 atomic_fetch_or32(u32* p, u32 v) { return atomicOr(p, v); 
 __device__ inline u32 atomic_fetch_and32(u32* p, u32 v) { return atomicAnd(p, v); }
 #endif
 
-// ---- per-thread counters of what a build asks of the runtime (ac_timings.launches / .readbacks) ---------------------------------------
+// ---- per-thread counters of what a build or a step asks of the runtime (ac_timings.launches / .readbacks; StepMeter below) -------------
+// The launchers and the read-backs of this file count themselves, in both builds: a kernel launch (the fused fills and the mailbox's
+// publishing kernel among them — the emulation has neither) and a host round trip each.
 struct RtCounters { u32 launches = 0, readbacks = 0; };
 inline RtCounters& rt_counters() { static thread_local RtCounters c; return c; }
 
@@ -597,8 +599,8 @@ inline void copy_d2h(void* h, const void* d, size_t bytes, stream_t s = 0) {
     }
 #endif
     copy_d2h_async(h, d, bytes, s);
+    rt_counters().readbacks++;      // (a host round trip like the two above; the emulation's only one)
 #ifndef AC_EMU
-    rt_counters().readbacks++;      // (a host round trip like the two above)
     AC_HIP_CHECK(hipStreamSynchronize(s));
 #endif
 }
@@ -608,6 +610,7 @@ class ReadBatch {
     void add(void* h, const void* d, size_t bytes) { if (bytes) items_.push_back(Item{h, d, bytes}); }
     void run(stream_t s = 0) {
 #ifdef AC_EMU
+        if (!items_.empty()) rt_counters().readbacks++;      // (add() keeps no empty item)
         for (auto& it : items_) memcpy(it.h, it.d, it.bytes);
         (void)s;
 #else
@@ -653,6 +656,84 @@ inline void stream_sync(stream_t s = 0) {
     AC_HIP_CHECK(hipStreamSynchronize(s));
 #endif
 }
+// ---- the step meter ----------------------------------------------------------------------------------------------------------------
+// How a step outside the build measures itself: what it asked of the runtime since the meter was made (the counters above, the same code in
+// both builds) and the device seconds of up to MAX_INTERVALS stretches of stream 0 — events on the device, the host's clock under the
+// emulation.  Made after the step's device is selected.  The events are created at an interval's first begin() and are the meter's own, not
+// from the ring of SideStream: nothing here may recycle an event a build still holds.  A step that runs batch after batch reads each
+// interval with take(), which hands its events to the next begin().
+class StepMeter {
+  public:
+    static const int MAX_INTERVALS = 2;
+    StepMeter() : before_(rt_counters()) {}
+    StepMeter(const StepMeter&) = delete;
+    StepMeter& operator=(const StepMeter&) = delete;
+    ~StepMeter() {
+#ifndef AC_EMU
+        for (Interval& iv : iv_) { if (iv.e0) (void)hipEventDestroy(iv.e0); if (iv.e1) (void)hipEventDestroy(iv.e1); }
+#endif
+    }
+    // Starts the next interval behind everything enqueued on stream 0 so far (queued fills leave first: they belong to what came before).
+    void begin() {
+        if (n_ == MAX_INTERVALS) throw DeviceError("step meter: more intervals than it holds (internal error)");
+        Interval& iv = iv_[n_++];
+        iv.ended = false;
+        flush_fills();
+#ifndef AC_EMU
+        if (!iv.e0) AC_HIP_CHECK(hipEventCreate(&iv.e0));
+        if (!iv.e1) AC_HIP_CHECK(hipEventCreate(&iv.e1));
+        AC_HIP_CHECK(hipEventRecord(iv.e0, 0));
+#else
+        iv.t0 = host_now();
+#endif
+    }
+    void end() {
+        if (n_ == 0 || iv_[n_ - 1].ended) throw DeviceError("step meter: end() without begin() (internal error)");
+        Interval& iv = iv_[n_ - 1];
+#ifndef AC_EMU
+        AC_HIP_CHECK(hipEventRecord(iv.e1, 0));
+#else
+        iv.t1 = host_now();
+#endif
+        iv.ended = true;
+    }
+    // Interval i in seconds, waiting for its end on the device: the same whether or not the caller has synchronised.  0 for one never begun or never ended.
+    double seconds(int i) {
+        if (i < 0 || i >= n_ || !iv_[i].ended) return 0;
+#ifndef AC_EMU
+        float ms = 0;
+        AC_HIP_CHECK(hipEventSynchronize(iv_[i].e1));
+        AC_HIP_CHECK(hipEventElapsedTime(&ms, iv_[i].e0, iv_[i].e1));
+        return 1e-3 * (double)ms;
+#else
+        return iv_[i].t1 - iv_[i].t0;
+#endif
+    }
+    double seconds() { double t = 0; for (int i = 0; i < n_; i++) t += seconds(i); return t; }
+    double take() { const double t = seconds(); n_ = 0; return t; }      // seconds(), and the next begin() is the first interval again
+    u32 launches() const { return rt_counters().launches - before_.launches; }
+    u32 read_backs() const { return rt_counters().readbacks - before_.readbacks; }
+    StepStats stats() { StepStats s; s.launches = launches(); s.read_backs = read_backs(); s.seconds_device = seconds(); return s; }
+    // A step's bulk copies (copy_d2h_async) and their one synchronisation: a host round trip like copy_d2h's.
+    void sync_copies() { stream_sync(); rt_counters().readbacks++; }
+
+  private:
+    struct Interval {
+#ifndef AC_EMU
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+#else
+        double t0 = 0, t1 = 0;
+#endif
+        bool ended = false;
+    };
+#ifdef AC_EMU
+    static double host_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+#endif
+    Interval iv_[MAX_INTERVALS];
+    int n_ = 0;
+    RtCounters before_;
+};
+
 template <class T> std::vector<T> to_host(const DBuf<T>& b, size_t n, stream_t s = 0) {
     std::vector<T> v(n);
     copy_d2h(v.data(), b.ptr(), n * sizeof(T), s);
@@ -837,6 +918,7 @@ template <class F> void launch(u64 n, const F& f, stream_t s = 0) {
 #ifdef AC_EMU
     // The serial emulation can visit the logical threads in three orders (AC_EMU_ORDER=0/1/2: ascending,
     // descending, pseudo-random) so the tests can check that no result depends on scheduling.
+    rt_counters().launches++;
     int order = emu_order();
     if (order == 1) { for (u64 i = n; i-- > 0;) f(i); }
     else if (order == 2) {
@@ -873,6 +955,7 @@ template <class F> void launch_full(u64 n, const F& f, stream_t s = 0) {
 #ifdef AC_EMU
     // whole wavefronts in lockstep (wave_rt.hpp): the functor's ballots and shuffles are the ones the device executes
     (void)s;
+    rt_counters().launches++;
     const u64 blocks = (n + 255) / 256;
     const F* fp = &f;
     for (u64 b0 = 0; b0 < blocks; b0 += 0xFFFFFFu)
@@ -895,12 +978,12 @@ template <class F> void launch_full(u64 n, const F& f, stream_t s = 0) {
 template <class K, class... A> void launch_wave_kernel_sized(K kernel, u64 blocks, unsigned threads, stream_t s, A... args) {
     if (blocks == 0) return;
     if (blocks > 0xFFFFFFULL) throw DeviceError("grid too large");
+    rt_counters().launches++;
 #ifdef AC_EMU
     (void)s;
     wv::launch_kernel(kernel, (unsigned)blocks, threads, args...);
 #else
     if (s == 0) flush_fills();
-    rt_counters().launches++;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, s, args...);
     AC_HIP_CHECK(hipGetLastError());
 #endif

@@ -1,10 +1,9 @@
 // Read-based unitig depths (ac_depth_*): the device side of set_read_depths (depth.rs:45-76).  A translation unit of its own: the k-mer
 // table lives as long as the caller's handle, across any number of graph builds, so nothing here comes from the build arena (which every
-// build resets) — the engine owns plain device allocations and frees them with the handle.  Timing uses two events of the engine's own
-// (not the 64-entry event ring of device_rt.hpp, whose entries a long-lived user would see recycled under it).
+// build resets) — the engine owns plain device allocations and frees them with the handle.  Timing is a StepMeter of the engine's own
+// (device_rt.hpp: its events are not from the 64-entry event ring, whose entries a long-lived user would see recycled under it).
 #include "graph_depth.hpp"
 
-#include <chrono>
 #include <thread>
 
 #include "device_rt.hpp"
@@ -14,8 +13,6 @@ namespace ac {
 #include "kernels_depth.inc"
 
 namespace {
-
-double depth_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 template <class T> struct OwnedDev {      // device memory that belongs to the engine
     T* p = nullptr; size_t cap = 0;
@@ -148,10 +145,7 @@ struct DepthEngine::Impl {
     std::vector<DepthGraphPlan> plans;
     OwnedDev<u64> d_q; OwnedDev<u8> d_present; OwnedDev<u32> d_qocc, d_qcnt;      // lookups
     DepthTotals tot;
-#ifndef AC_EMU
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Impl() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-#endif
+    StepMeter meter;      // one interval per batch of reads
 
     struct Text { u64 n_words, n_seqs; };
     template <class Src> Text upload_text(const Src& src, const std::vector<u64>& toff) {
@@ -203,9 +197,6 @@ DepthEngine::DepthEngine(uint32_t k, const std::vector<DepthGraphView>& graphs, 
     m.err.ensure(1); m.err.fill(0, 1);
     m.d_totals.ensure(8); m.d_totals.fill(0, 8);
     m.tot.table_slots = cap;
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventCreate(&m.e0)); AC_HIP_CHECK(hipEventCreate(&m.e1));
-#endif
     if (!seq.empty()) {
         const Impl::Text x = m.upload_text([&](u64 r) { return seq[r]; }, m.asm_toff);
         m.reset_read_sums(x.n_seqs);
@@ -252,25 +243,13 @@ void DepthEngine::add_reads(const uint8_t* bases, const uint64_t* off, uint64_t 
         const Impl::Text x = m.upload_text([&](u64 r) { return bases + off[r0 + r]; }, toff);
         m.reset_read_sums(x.n_seqs);
         m.d_hitslot.ensure(x.n_words * 32);
-        const double t0 = depth_now();
-#ifndef AC_EMU
-        flush_fills();
-        AC_HIP_CHECK(hipEventRecord(m.e0, 0));
-#endif
+        m.meter.begin();
         m.roll<1>(x, m.d_hitslot.p);
         launch_full(x.n_seqs, DepthAcceptFunctor{m.d_rk.p, m.d_rh.p, m.d_rf.p, m.d_rl.p, m.d_toff.p, m.d_acc.p, m.d_totals.p, m.k});
         launch_wave_kernel(depth_commit_kernel, (x.n_words * 32 + 4 * DEPTH_WAVE_TILE - 1) / (4 * DEPTH_WAVE_TILE), 0, (const u32*)m.d_hitslot.p,
                            x.n_words * 32, (const u64*)m.d_toff.p, (const u32*)m.d_wread.p, (const u8*)m.d_acc.p, m.t.cnt);
-#ifndef AC_EMU
-        AC_HIP_CHECK(hipEventRecord(m.e1, 0));
-        AC_HIP_CHECK(hipEventSynchronize(m.e1));
-        float ms = 0;
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, m.e0, m.e1));
-        m.tot.seconds_device += 1e-3 * (double)ms;
-        (void)t0;
-#else
-        m.tot.seconds_device += depth_now() - t0;
-#endif
+        m.meter.end();
+        m.tot.seconds_device += m.meter.take();      // (waits for the batch: the staging planes are packed anew for the next one)
         m.tot.batches++; m.tot.launches += 3;
         r0 = r1;
     }

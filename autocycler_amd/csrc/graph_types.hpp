@@ -52,6 +52,14 @@ struct Link {
 
 struct Position { uint32_t pos; uint16_t seq_id_and_strand; };   // position.rs:18-22
 
+// What a graph step asked of the device runtime, as its StepMeter (device_rt.hpp) read it: kernel launches, host round trips, and the device
+// seconds of its timed intervals.  A step that runs another one inside adds that one's record to its own.
+struct StepStats {
+    uint32_t launches = 0, read_backs = 0;
+    double seconds_device = 0;
+    StepStats& operator+=(const StepStats& o) { launches += o.launches; read_backs += o.read_backs; seconds_device += o.seconds_device; return *this; }
+};
+
 // The final UnitigGraph (after simplify_structure), in final order (number = index + 1).  The bulk arrays live
 // in host blocks filled straight from the device.
 struct FinalGraph {

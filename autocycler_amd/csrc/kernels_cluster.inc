@@ -174,32 +174,16 @@ static void cluster_merge_loop(const double* d_asym, u32 S, std::vector<ClusterR
     launch(S, ClusterInitFunctor{active.ptr(), size.ptr()});
     launch_wave_kernel(cluster_refresh_kernel, ((u64)S + 3) / 4, 0, S, 1, (const double*)avg.ptr(), (const u32*)active.ptr(), nn_val.ptr(), nn_col.ptr(), st.ptr());
     launches += 3;
-    const double t0 = now_s();
-#ifndef AC_EMU
-    hipEvent_t e0, e1;
-    AC_HIP_CHECK(hipEventCreate(&e0));
-    struct EvFree { hipEvent_t* a; hipEvent_t* b; ~EvFree() { if (a) (void)hipEventDestroy(*a); if (b) (void)hipEventDestroy(*b); } } evfree{&e0, nullptr};
-    AC_HIP_CHECK(hipEventCreate(&e1));
-    evfree.b = &e1;
-    flush_fills();
-    AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
+    StepMeter meter;
+    meter.begin();
     for (u32 m = 0; m + 1 < S; m++) {
         launch_wave_kernel(cluster_pick_kernel, 1, 0, S, (const double*)nn_val.ptr(), (const u32*)nn_col.ptr(), active.ptr(), size.ptr(), st.ptr(), d_merges.ptr());
         launch(S, ClusterFoldFunctor{S, sum.ptr(), avg.ptr(), active.ptr(), size.ptr(), st.ptr()});
         launch_wave_kernel(cluster_refresh_kernel, ((u64)S + 3) / 4, 0, S, 0, (const double*)avg.ptr(), (const u32*)active.ptr(), nn_val.ptr(), nn_col.ptr(), st.ptr());
         launches += 3;
     }
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e1, 0));
-    AC_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    const double seconds = 1e-3 * (double)ms;
-    (void)t0;
-#else
-    const double seconds = now_s() - t0;
-#endif
+    meter.end();
+    const double seconds = meter.seconds();
     ClusterStateDev h_st;
     std::vector<ClusterMergeDev> h_merges(S);
     copy_d2h(&h_st, st.ptr(), sizeof h_st);

@@ -137,10 +137,7 @@ struct ClusterQcSession {
     DBuf<u32> bad;
     ClusterQcDeviceStats* st;
     u64 pair_batch;
-#ifndef AC_EMU
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~ClusterQcSession() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-#endif
+    StepMeter meter;      // one interval per evaluation
 
     void evaluate(const ClusterQcPlan& plan, std::vector<u32>* verdicts) {
         Arena& arena = Arena::device();
@@ -160,11 +157,7 @@ struct ClusterQcSession {
         DBuf<u32> d_out(words);
         copy_h2d(d_base.ptr(), plan.base.data(), (size_t)n * sizeof(ClusterQcEntity));
         copy_h2d(d_alts.ptr(), plan.alts.data(), (size_t)A * sizeof(ClusterQcAlt));
-        const double t0 = now_s();
-#ifndef AC_EMU
-        flush_fills();
-        AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
+        meter.begin();
         for (u64 b0 = 0; b0 < entries; b0 += pair_batch) {
             const u64 b1 = std::min(entries, b0 + pair_batch);
             launch_wave_kernel(cluster_qc_pairs_kernel, (b1 - b0 + 3) / 4, 0, b0, b1, n, W, (const u64*)bits.ptr(), (const ClusterQcEntity*)d_base.ptr(),
@@ -174,21 +167,11 @@ struct ClusterQcSession {
         launch_wave_kernel_sized(cluster_qc_chain_kernel, A, 64u, 0, n, (const ClusterQcEntity*)d_base.ptr(), (const ClusterQcAlt*)d_alts.ptr(),
                                  (const u8*)d_contained.ptr(), (const u32*)bad.ptr(), d_out.ptr());
         st->launches++;
-#ifndef AC_EMU
-        AC_HIP_CHECK(hipEventRecord(e1, 0));
-#endif
+        meter.end();
         std::vector<u32> h_out(words);
         copy_d2h(h_out.data(), d_out.ptr(), (size_t)words * 4);
         st->readbacks++; st->evaluations++; st->bytes_read_back += words * 4;
-#ifndef AC_EMU
-        AC_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        st->seconds += 1e-3 * (double)ms;
-        (void)t0;
-#else
-        st->seconds += now_s() - t0;
-#endif
+        st->seconds += meter.take();
         st->alternatives += A; st->pairs_counted += plan.pairs_counted();
         arena.rewind(mark);
         if (h_out[0]) throw DeviceError("cluster: the distance matrix holds a NaN, an infinite or a negative value");
@@ -207,10 +190,6 @@ void cluster_qc_device(const double* asym, uint32_t n, const uint32_t* dfs_tip, 
         const long long v = e ? atoll(e) : 0;
         s.pair_batch = v > 0 ? std::min<u64>((u64)v, (u64)1 << 25) : CLUSTER_QC_DEFAULT_PAIR_BATCH;
     }
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventCreate(&s.e0));
-    AC_HIP_CHECK(hipEventCreate(&s.e1));
-#endif
     s.bits.alloc((u64)n * s.W);
     s.bad.alloc(1);
     s.bad.fill_bytes(0);

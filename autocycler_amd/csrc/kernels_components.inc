@@ -32,6 +32,29 @@ static const u32 COMP_ERR_RANGE = 1, COMP_ERR_BOUND = 2;
 static const u32 COMP_DEAD = 0xFFFFFFFFu;
 struct CompHeader { u64 n_components, n_alive, first_bad_link, reserved; };
 
+// ---- what the three graph steps share (this file, kernels_merge.inc, kernels_subset.inc) ----
+static int bit_width(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
+static u32 jump_rounds(u64 n) { u32 rounds = 1; while (((u64)1 << (rounds - 1)) < n) rounds++; return rounds; }      // ceil(log2 n) + 1: pointer jumping over at most n members
+// A link entry's two ends: LINK_NO_UNITIG, LINK_DEAD (it touches a unitig that is not alive: the entry is ignored), or LINK_OK with the two
+// unitig indices and the planes of the lists build_links_from_gfa puts the entry into — a's next list, b's prev list.
+static const int LINK_OK = 0, LINK_NO_UNITIG = 1, LINK_DEAD = 2;
+struct LinkEnds { u32 ua, ub, la, lb; };
+AC_D int link_ends(const Link& l, u32 n, const u8* alive, LinkEnds* e) {
+    const u32 na = l.na(), nb = l.nb();
+    if (na == 0 || nb == 0 || na > n || nb > n) return LINK_NO_UNITIG;
+    e->ua = na - 1; e->ub = nb - 1;
+    if (alive && (!alive[e->ua] || !alive[e->ub])) return LINK_DEAD;
+    e->la = l.a > 0 ? COMP_FN : COMP_RN; e->lb = l.b > 0 ? COMP_FP : COMP_RP;
+    return LINK_OK;
+}
+// The entry in its two lists: their lengths, and one target each — whichever entry stores last, read only where the list has one entry.
+AC_D void link_into_lists(const Link& l, const LinkEnds& e, u32 n, u32* deg, int32_t* target) {
+    atomic_add32(&deg[(u64)e.la * n + e.ua], 1u); target[(u64)e.la * n + e.ua] = l.b;
+    atomic_add32(&deg[(u64)e.lb * n + e.ub], 1u); target[(u64)e.lb * n + e.ub] = l.a;
+}
+// The key of an entry that takes no part (it sorts behind every real key of two key_bits halves).
+AC_D u64 link_key_dropped(int key_bits) { return key_bits == 32 ? ~0ULL : ((1ULL << (2 * key_bits)) - 1ULL); }
+
 AC_D u32 comp_find(u32* parent, u32 x, u32 n, u32* err) {
     for (u32 s = 0; s <= n; s++) {
         const u32 p = atomic_load32(&parent[x]);
@@ -63,23 +86,22 @@ struct CompCensusFunctor {
     const Link* links; u32 n; const u8* alive; int key_bits;      // key_bits: bits of one half of a key
     u32* deg; int32_t* target; u32* notself; u32* parent; u64* key; u32* key_unitig; u32* err; CompHeader* hdr;
     AC_D void operator()(u64 i) const {
-        const u64 dropped = key_bits == 32 ? ~0ULL : ((1ULL << (2 * key_bits)) - 1ULL);
         const int64_t a = links[i].a, b = links[i].b;
-        const int64_t na = a < 0 ? -a : a, nb = b < 0 ? -b : b;
-        key[i] = dropped; key_unitig[i] = 0;
-        if (na == 0 || nb == 0 || na > (int64_t)n || nb > (int64_t)n) {
+        key[i] = link_key_dropped(key_bits); key_unitig[i] = 0;
+        LinkEnds e;
+        const int ends = link_ends(links[i], n, alive, &e);
+        if (ends == LINK_NO_UNITIG) {
             atomic_or32(err, COMP_ERR_RANGE);
             atomic_min64(&hdr->first_bad_link, i);
             return;
         }
-        const u32 ua = (u32)na - 1, ub = (u32)nb - 1;
-        if (alive && (!alive[ua] || !alive[ub])) return;
-        // a's next list, b's prev list; the notself bits: an entry that is_isolated_and_linear's all() rejects
-        const u32 la = a > 0 ? COMP_FN : COMP_RN, lb = b > 0 ? COMP_FP : COMP_RP;
-        atomic_add32(&deg[(u64)la * n + ua], 1u); target[(u64)la * n + ua] = (int32_t)b;
-        atomic_add32(&deg[(u64)lb * n + ub], 1u); target[(u64)lb * n + ub] = (int32_t)a;
-        if (b != (a > 0 ? -na : na)) atomic_or32(&notself[ua], 1u << la);      // forward_next: myself, reverse; reverse_next: myself, forward
-        if (a != (b > 0 ? -nb : nb)) atomic_or32(&notself[ub], 1u << lb);      // forward_prev: myself, reverse; reverse_prev: myself, forward
+        if (ends == LINK_DEAD) return;
+        const u32 ua = e.ua, ub = e.ub;
+        const int64_t na = (int64_t)ua + 1, nb = (int64_t)ub + 1;
+        link_into_lists(links[i], e, n, deg, target);
+        // the notself bits: an entry that is_isolated_and_linear's all() rejects
+        if (b != (a > 0 ? -na : na)) atomic_or32(&notself[ua], 1u << e.la);      // forward_next: myself, reverse; reverse_next: myself, forward
+        if (a != (b > 0 ? -nb : nb)) atomic_or32(&notself[ub], 1u << e.lb);      // forward_prev: myself, reverse; reverse_prev: myself, forward
         // link_count's one_way entry: the larger of (a, b) and (-b, -a) as tuples, as a key that keeps the tuples' order
         const bool keep = a > -b || (a == -b && b >= -a);
         const int64_t ca = keep ? a : -b, cb = keep ? b : -a;
@@ -193,7 +215,7 @@ struct CompLinkCountFunctor {
     u64* c_links_all; u64* c_links_one_way;
     AC_D void operator()(u64 j, bool valid) const {
         const int lane = wv::lane();
-        const u64 dropped = key_bits == 32 ? ~0ULL : ((1ULL << (2 * key_bits)) - 1ULL);
+        const u64 dropped = link_key_dropped(key_bits);
         u32 c = COMP_DEAD; u64 counts = 0;      // one_way | all << 32
         if (valid) {
             const u64 k = key[j];
@@ -251,8 +273,6 @@ struct CompRecordsFunctor {
     }
 };
 
-static int comp_bit_width(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
-
 void components_device(uint32_t n, const Link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* marked,
                        ComponentsResult* out) {
     *out = ComponentsResult();
@@ -267,19 +287,10 @@ void components_device(uint32_t n, const Link* links, uint64_t n_links, const ui
     }
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    // (events of this feature's own, not from the ring of device_rt.hpp: nothing here may recycle an event a build still holds)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvFree { hipEvent_t* a; hipEvent_t* b; ~EvFree() { if (*a) (void)hipEventDestroy(*a); if (*b) (void)hipEventDestroy(*b); } } evfree{&e0, &e1};
-    AC_HIP_CHECK(hipEventCreate(&e0));
-    AC_HIP_CHECK(hipEventCreate(&e1));
-    const RtCounters before = rt_counters();
-#endif
-    u32 launched = 0;      // (the emulation's count: the device build reads the runtime's own counters)
+    StepMeter meter;
     const u64 nl = n_links;
-    const int key_bits = comp_bit_width(2 * (u64)n), comp_bits = comp_bit_width((u64)n);
-    u32 rounds = 1;
-    while (((u64)1 << (rounds - 1)) < (u64)n) rounds++;      // ceil(log2 n) + 1
+    const int key_bits = bit_width(2 * (u64)n), comp_bits = bit_width((u64)n);
+    const u32 rounds = jump_rounds(n);
 
     DBuf<Link> d_links(nl);
     DBuf<u32> d_len(unitig_len ? n : 0); DBuf<u8> d_alive(alive ? n : 0), d_marked(marked ? n : 0);
@@ -305,38 +316,27 @@ void components_device(uint32_t n, const Link* links, uint64_t n_links, const ui
     RadixScratch sort_members, sort_links;
     sort_members.prepare(n, comp_bits);
     sort_links.prepare(nl, 2 * key_bits);
-    auto sort_launches = [](size_t items, int bits) -> u32 { return items > 1 && bits > 0 ? 1u + (u32)std::min((bits + 7) / 8, 8) : 0u; };
 
-    const double t0 = now_s();
-#ifndef AC_EMU
-    flush_fills();
-    AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
-    launch(n, CompInitFunctor{d_parent.ptr()}); launched++;
+    meter.begin();
+    launch(n, CompInitFunctor{d_parent.ptr()});
     if (nl) {
         launch(nl, CompCensusFunctor{d_links.ptr(), n, p_alive, key_bits, d_deg.ptr(), d_target.ptr(), d_notself.ptr(), d_parent.ptr(), d_key.ptr(), d_key_unitig.ptr(),
                                      d_err.ptr(), d_hdr.ptr()});
-        launched++;
-        for (u32 r = 0; r < rounds; r++) { launch(n, CompJumpFunctor{d_parent.ptr(), d_changed.ptr(), r}); launched++; }
+        for (u32 r = 0; r < rounds; r++) launch(n, CompJumpFunctor{d_parent.ptr(), d_changed.ptr(), r});
     }
-    launch(n, CompRootsFunctor{d_parent.ptr(), p_alive, n, d_deg.ptr(), d_target.ptr(), d_notself.ptr(), d_is_root.ptr(), d_flags.ptr(), d_err.ptr()}); launched++;
-    exclusive_scan_u32(d_is_root.ptr(), d_root_rank.ptr(), n); launched++;
-    launch(n, CompLabelFunctor{d_parent.ptr(), d_is_root.ptr(), d_root_rank.ptr(), p_alive, n, d_component_of.ptr(), d_sort_key.ptr(), d_sort_val.ptr(), d_hdr.ptr()}); launched++;
-    sort_pairs_u64_u32(d_sort_key, d_sort_val, n, comp_bits, 0, 0, &sort_members); launched += sort_launches(n, comp_bits);
+    launch(n, CompRootsFunctor{d_parent.ptr(), p_alive, n, d_deg.ptr(), d_target.ptr(), d_notself.ptr(), d_is_root.ptr(), d_flags.ptr(), d_err.ptr()});
+    exclusive_scan_u32(d_is_root.ptr(), d_root_rank.ptr(), n);
+    launch(n, CompLabelFunctor{d_parent.ptr(), d_is_root.ptr(), d_root_rank.ptr(), p_alive, n, d_component_of.ptr(), d_sort_key.ptr(), d_sort_val.ptr(), d_hdr.ptr()});
+    sort_pairs_u64_u32(d_sort_key, d_sort_val, n, comp_bits, 0, 0, &sort_members);
     launch_full(n, CompSegmentsFunctor{d_sort_key.ptr(), d_sort_val.ptr(), n, p_len, p_marked, d_deg.ptr(), d_off_in.ptr(), d_length.ptr(), d_ends_marked.ptr(),
                                        d_not_one.ptr(), d_hdr.ptr()});
-    launched++;
     if (nl) {
-        sort_pairs_u64_u32(d_key, d_key_unitig, nl, 2 * key_bits, 0, 0, &sort_links); launched += sort_launches(nl, 2 * key_bits);
+        sort_pairs_u64_u32(d_key, d_key_unitig, nl, 2 * key_bits, 0, 0, &sort_links);
         launch_full(nl, CompLinkCountFunctor{d_key.ptr(), d_key_unitig.ptr(), nl, n, key_bits, d_component_of.ptr(), d_links_all.ptr(), d_links_one_way.ptr()});
-        launched++;
     }
     launch((u64)n + 1, CompRecordsFunctor{d_hdr.ptr(), n, d_off_in.ptr(), d_sort_val.ptr(), d_length.ptr(), d_ends_marked.ptr(), d_not_one.ptr(), d_links_all.ptr(),
                                           d_links_one_way.ptr(), d_target.ptr(), d_off.ptr(), d_stamp.ptr(), d_records.ptr(), d_err.ptr()});
-    launched++;
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e1, 0));
-#endif
+    meter.end();
     // the read-back: the header and the error word say how much there is to fetch (the arrays are sized by n; what crosses is sized by the
     // components and the alive unitigs), then everything else behind one synchronisation
     CompHeader h; u32 err[2] = {0, 0};
@@ -345,17 +345,6 @@ void components_device(uint32_t n, const Link* links, uint64_t n_links, const ui
         rb.add(&h, d_hdr.ptr(), sizeof h); rb.add(err, d_err.ptr(), sizeof err);
         rb.run();
     }
-#ifndef AC_EMU
-    {
-        float ms = 0;
-        AC_HIP_CHECK(hipEventSynchronize(e1));
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        out->seconds_device = 1e-3 * (double)ms;
-        (void)t0;
-    }
-#else
-    out->seconds_device = now_s() - t0;
-#endif
     if (err[0] & COMP_ERR_RANGE) {
         const u64 i = h.first_bad_link < nl ? h.first_bad_link : 0;
         throw DeviceError(components_bad_link_message(i, links[i].a, links[i].b, n));
@@ -369,15 +358,7 @@ void components_device(uint32_t n, const Link* links, uint64_t n_links, const ui
     copy_d2h_async(out->member_off.data(), d_off.ptr(), (nc + 1) * 8);
     copy_d2h_async(out->members.data(), d_sort_val.ptr(), na * 4);
     copy_d2h_async(out->flags.data(), d_flags.ptr(), n);
-    stream_sync();
-#ifndef AC_EMU
-    rt_counters().readbacks++;      // (the bulk copies and their one synchronisation: a host round trip like copy_d2h's)
-    out->launches = rt_counters().launches - before.launches;
-    out->read_backs = rt_counters().readbacks - before.readbacks;
-    (void)launched;
-#else
-    out->launches = launched;
-    out->read_backs = 2;
-#endif
+    meter.sync_copies();
+    out->stats = meter.stats();
     components_finish(out);
 }

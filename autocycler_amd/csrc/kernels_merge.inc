@@ -39,7 +39,6 @@ struct MergeCounts { u64 n_chains, n_members, n_bases, n_links_after, reserved[2
 AC_D u32 merge_node(int32_t e) { return e > 0 ? 2u * ((u32)e - 1u) : 2u * ((u32)(-(int64_t)e) - 1u) + 1u; }
 AC_D int32_t merge_signed(u32 x) { return (x & 1u) ? -(int32_t)((x >> 1) + 1u) : (int32_t)((x >> 1) + 1u); }
 AC_D u64 merge_key(int64_t a, int64_t b, u64 offset, int key_bits) { return ((u64)(a + (int64_t)offset) << key_bits) | (u64)(b + (int64_t)offset); }
-AC_D u64 merge_dropped(int key_bits) { return key_bits == 32 ? ~0ULL : ((1ULL << (2 * key_bits)) - 1ULL); }
 // is `k` among key[0, n) (ascending)?
 AC_D bool merge_has_key(const u64* key, u64 n, u64 k) {
     u64 lo = 0, hi = n;
@@ -73,14 +72,11 @@ struct MergeCensusFunctor {
     u32* deg; int32_t* target; u32* fixed; u64* key; u32* key_index;
     AC_D void operator()(u64 i) const {
         const int64_t a = links[i].a, b = links[i].b;
-        const int64_t na = a < 0 ? -a : a, nb = b < 0 ? -b : b;
-        key[i] = merge_dropped(key_bits); key_index[i] = (u32)i;
-        if (na == 0 || nb == 0 || na > (int64_t)n || nb > (int64_t)n) return;      // (components_device has refused these already)
-        const u32 ua = (u32)na - 1, ub = (u32)nb - 1;
-        if (alive && (!alive[ua] || !alive[ub])) return;
-        const u32 la = a > 0 ? COMP_FN : COMP_RN, lb = b > 0 ? COMP_FP : COMP_RP;
-        atomic_add32(&deg[(u64)la * n + ua], 1u); target[(u64)la * n + ua] = (int32_t)b;
-        atomic_add32(&deg[(u64)lb * n + ub], 1u); target[(u64)lb * n + ub] = (int32_t)a;
+        key[i] = link_key_dropped(key_bits); key_index[i] = (u32)i;
+        LinkEnds e;
+        if (link_ends(links[i], n, alive, &e) != LINK_OK) return;      // (components_device has refused the entries that name no unitig already)
+        const u32 ua = e.ua, ub = e.ub;
+        link_into_lists(links[i], e, n, deg, target);
         {
             // a is in b's forward_prev: upstream of a fixed start (:214-219); b is in a's forward_next: downstream of a fixed end (:222-227)
             if (b > 0 && (seed[ub] & MERGE_FIXED_START)) atomic_or32(&fixed[ua], a > 0 ? MERGE_FIXED_END : MERGE_FIXED_START);
@@ -95,7 +91,7 @@ struct MergeLinkCheckFunctor {
     const u64* key; const u32* key_index; u64 n_links; u32 n; int key_bits; u64* first_bad;      // [0]: duplicate, [1]: no reverse complement
     AC_D void operator()(u64 j) const {
         const u64 k = key[j];
-        if (k == merge_dropped(key_bits)) return;
+        if (k == link_key_dropped(key_bits)) return;
         if (j > 0 && key[j - 1] == k) atomic_min64(&first_bad[0], (u64)key_index[j]);
         const int64_t a = (int64_t)(k >> key_bits) - (int64_t)n, b = (int64_t)(k & ((1ULL << key_bits) - 1ULL)) - (int64_t)n;
         if (!merge_has_key(key, n_links, merge_key(-b, -a, n, key_bits))) atomic_min64(&first_bad[1], (u64)key_index[j]);
@@ -234,12 +230,11 @@ struct MergeRelabelFunctor {
     const Link* links; u32 n; const u8* alive; const u32* succ; const u32* chain_of; const u32* pos_in_chain; const u8* strand_in_chain; const u32* k_members;
     u64 offset; int key_bits; u64* key; u32* val; u32* err;
     AC_D void operator()(u64 i) const {
-        key[i] = merge_dropped(key_bits); val[i] = (u32)i;
+        key[i] = link_key_dropped(key_bits); val[i] = (u32)i;
         int64_t a = links[i].a, b = links[i].b;
-        const int64_t na = a < 0 ? -a : a, nb = b < 0 ? -b : b;
-        if (na == 0 || nb == 0 || na > (int64_t)n || nb > (int64_t)n) return;
-        const u32 ua = (u32)na - 1, ub = (u32)nb - 1;
-        if (alive && (!alive[ua] || !alive[ub])) return;
+        LinkEnds e;
+        if (link_ends(links[i], n, alive, &e) != LINK_OK) return;
+        const u32 ua = e.ua, ub = e.ub;
         const u32 ca = chain_of[ua], cb = chain_of[ub];
         if (ca != MERGE_NONE && succ[merge_node((int32_t)a)] == merge_node((int32_t)b)) return;      // a join of the chain, or the mirror image of one
         if (ca != MERGE_NONE) {      // as a source: the last member on its chain strand is +, the first on the other strand is -
@@ -263,7 +258,7 @@ struct MergeRelabelFunctor {
 struct MergeDecodeFunctor {
     const u64* key; u64 n_links; u64 offset; int key_bits; Link* out; MergeCounts* counts;
     AC_D void operator()(u64 j) const {
-        const u64 k = key[j], dropped = merge_dropped(key_bits);
+        const u64 k = key[j], dropped = link_key_dropped(key_bits);
         if (k == dropped) return;
         out[j].a = (int32_t)((int64_t)(k >> key_bits) - (int64_t)offset);
         out[j].b = (int32_t)((int64_t)(k & ((1ULL << key_bits) - 1ULL)) - (int64_t)offset);
@@ -355,8 +350,6 @@ struct MergeCopyFunctor {
     }
 };
 
-static int merge_bit_width(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
-
 void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
     *out = MergeResult();
     const u32 n = in.n_unitigs;
@@ -371,30 +364,21 @@ void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
     // connected components with their circular-loop flags, on the device (kernels_components.inc): it refuses links that name no unitig,
     // and fix_circular_loops (:374-384) is the lowest member of every loop
     std::vector<u8> seed(in.seed_fixed, in.seed_fixed + n);
-    u32 comp_launches = 0, comp_read_backs = 0;
-    double comp_seconds = 0;
     {
         ComponentsResult comp;
         components_device(n, in.links, nl, in.unitig_len, in.alive, nullptr, &comp);
         for (const ComponentRecord& rec : comp.records)
             if (rec.circular_loop) seed[rec.first - 1] |= MERGE_SEED_LOOP;
-        comp_launches = comp.launches; comp_read_backs = comp.read_backs; comp_seconds = comp.seconds_device;
+        out->stats = comp.stats;
     }
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    struct EvFree { hipEvent_t* e[4]; ~EvFree() { for (auto p : e) if (*p) (void)hipEventDestroy(*p); } } evfree{{&e0, &e1, &e2, &e3}};
-    AC_HIP_CHECK(hipEventCreate(&e0)); AC_HIP_CHECK(hipEventCreate(&e1)); AC_HIP_CHECK(hipEventCreate(&e2)); AC_HIP_CHECK(hipEventCreate(&e3));
-    const RtCounters before = rt_counters();
-#endif
-    u32 launched = 0;      // (the emulation's count: the device build reads the runtime's own counters)
+    StepMeter meter;
     const u64 nodes = 2 * (u64)n, nc_max = (u64)n + 1;      // (a valid input has at most n / 2 chains; one whose links are no closed set, refused below, up to n)
     const u64 offset_after = (u64)n + nc_max;      // no number after the merge is above this
-    const int key_bits = merge_bit_width(2 * (u64)n), key_bits_after = merge_bit_width(2 * offset_after);
+    const int key_bits = bit_width(2 * (u64)n), key_bits_after = bit_width(2 * offset_after);
     if (key_bits_after > 32) throw DeviceError("merge plan: more unitigs than a 64-bit link key after the merge can name");
-    u32 rounds = 1;
-    while (((u64)1 << (rounds - 1)) < (u64)n) rounds++;      // ceil(log2 n) + 1: a path has at most n members
+    const u32 rounds = jump_rounds(n);      // a path has at most n members
     const bool with_paths = in.path != nullptr && in.n_path > 0;
     const bool with_seq = in.seq_bytes != nullptr;
 
@@ -431,51 +415,38 @@ void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
     RadixScratch sort_links, sort_after;
     sort_links.prepare(nl, 2 * key_bits);
     sort_after.prepare(nl, 2 * key_bits_after);
-    auto sort_launches = [](size_t items, int bits) -> u32 { return items > 1 && bits > 0 ? 1u + (u32)std::min((bits + 7) / 8, 8) : 0u; };
 
-    const double t0 = now_s();
-#ifndef AC_EMU
-    flush_fills();
-    AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
-    if (with_paths) { launch(in.n_path, MergeHistogramFunctor{d_path.ptr(), n, d_fwd.ptr(), d_rev.ptr()}); launched++; }
-    launch(n, MergeInitFunctor{d_seed.ptr(), d_fixed.ptr()}); launched++;
+    meter.begin();
+    if (with_paths) launch(in.n_path, MergeHistogramFunctor{d_path.ptr(), n, d_fwd.ptr(), d_rev.ptr()});
+    launch(n, MergeInitFunctor{d_seed.ptr(), d_fixed.ptr()});
     if (nl) {
         launch(nl, MergeCensusFunctor{d_links.ptr(), n, p_alive, d_seed.ptr(), key_bits, d_deg.ptr(), d_target.ptr(), d_fixed.ptr(), d_key.ptr(), d_key_index.ptr()});
-        launched++;
-        sort_pairs_u64_u32(d_key, d_key_index, nl, 2 * key_bits, 0, 0, &sort_links); launched += sort_launches(nl, 2 * key_bits);
-        launch(nl, MergeLinkCheckFunctor{d_key.ptr(), d_key_index.ptr(), nl, n, key_bits, d_first_bad.ptr()}); launched++;
+        sort_pairs_u64_u32(d_key, d_key_index, nl, 2 * key_bits, 0, 0, &sort_links);
+        launch(nl, MergeLinkCheckFunctor{d_key.ptr(), d_key_index.ptr(), nl, n, key_bits, d_first_bad.ptr()});
     }
     const MergeGraphView view{n, d_deg.ptr(), d_target.ptr(), d_fixed.ptr()};
-    launch(nodes, MergeSuccFunctor{view, p_alive, d_succ.ptr(), d_pred.ptr(), d_literal_head.ptr(), d_fixed_out.ptr()}); launched++;
+    launch(nodes, MergeSuccFunctor{view, p_alive, d_succ.ptr(), d_pred.ptr(), d_literal_head.ptr(), d_fixed_out.ptr()});
     MergeRank ra{d_start_a.ptr(), d_hops_a.ptr(), d_bases_a.ptr()}, rb{d_start_b.ptr(), d_hops_b.ptr(), d_bases_b.ptr()};
-    launch(nodes, MergeRankInitFunctor{d_pred.ptr(), d_len.ptr(), ra}); launched++;
-    for (u32 r = 0; r < rounds; r++) { launch(nodes, MergeRankJumpFunctor{ra, rb}); launched++; std::swap(ra, rb); }
+    launch(nodes, MergeRankInitFunctor{d_pred.ptr(), d_len.ptr(), ra});
+    for (u32 r = 0; r < rounds; r++) { launch(nodes, MergeRankJumpFunctor{ra, rb}); std::swap(ra, rb); }
     launch(nodes, MergeSelectFunctor{d_succ.ptr(), d_pred.ptr(), d_literal_head.ptr(), p_alive, d_len.ptr(), ra, d_c_flag.ptr(), d_c_head.ptr(), d_c_tail.ptr(),
                                      d_c_members.ptr(), d_c_length.ptr()});
-    launched++;
-    exclusive_scan_u32(d_c_flag.ptr(), d_c_rank.ptr(), n); launched++;
+    exclusive_scan_u32(d_c_flag.ptr(), d_c_rank.ptr(), n);
     launch(n, MergeCompactFunctor{n, d_c_flag.ptr(), d_c_rank.ptr(), d_c_head.ptr(), d_c_tail.ptr(), d_c_members.ptr(), d_c_length.ptr(), d_k_head.ptr(), d_k_tail.ptr(),
                                   d_k_members.ptr(), d_k_length.ptr(), d_chain_of_head.ptr(), d_counts.ptr()});
-    launched++;
-    exclusive_scan_u32(d_k_members.ptr(), d_k_member_off.ptr(), nc_max); launched++;
-    exclusive_scan_u64(d_k_length.ptr(), d_k_seq_off.ptr(), nc_max); launched++;
+    exclusive_scan_u32(d_k_members.ptr(), d_k_member_off.ptr(), nc_max);
+    exclusive_scan_u64(d_k_length.ptr(), d_k_seq_off.ptr(), nc_max);
     launch(nodes, MergeMembersFunctor{d_pred.ptr(), p_alive, ra, d_chain_of_head.ptr(), d_k_member_off.ptr(), d_k_seq_off.ptr(), d_members.ptr(), d_member_seq_off.ptr(),
                                       d_chain_of.ptr(), d_pos_in_chain.ptr(), d_strand_in_chain.ptr(), n, d_err.ptr()});
-    launched++;
     launch(nc_max, MergeRecordsFunctor{d_counts.ptr(), n, key_bits, d_key.ptr(), nl, d_k_head.ptr(), d_k_tail.ptr(), d_k_members.ptr(), d_k_length.ptr(), d_k_member_off.ptr(),
                                        d_k_seq_off.ptr(), d_records.ptr(), d_member_seq_off.ptr()});
-    launched++;
     if (nl) {
         launch(nl, MergeRelabelFunctor{d_links.ptr(), n, p_alive, d_succ.ptr(), d_chain_of.ptr(), d_pos_in_chain.ptr(), d_strand_in_chain.ptr(), d_k_members.ptr(), offset_after,
                                        key_bits_after, d_key_after.ptr(), d_val_after.ptr(), d_err.ptr()});
-        launched++;
-        sort_pairs_u64_u32(d_key_after, d_val_after, nl, 2 * key_bits_after, 0, 0, &sort_after); launched += sort_launches(nl, 2 * key_bits_after);
-        launch(nl, MergeDecodeFunctor{d_key_after.ptr(), nl, offset_after, key_bits_after, d_links_after.ptr(), d_counts.ptr()}); launched++;
+        sort_pairs_u64_u32(d_key_after, d_val_after, nl, 2 * key_bits_after, 0, 0, &sort_after);
+        launch(nl, MergeDecodeFunctor{d_key_after.ptr(), nl, offset_after, key_bits_after, d_links_after.ptr(), d_counts.ptr()});
     }
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e1, 0));
-#endif
+    meter.end();
     // the header: errors and sizes (the arrays are sized by n; what crosses is sized by the chains)
     MergeCounts h; u64 first_bad[2] = {~0ULL, ~0ULL}; u32 err[2] = {0, 0};
     {
@@ -495,19 +466,13 @@ void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
         copy_h2d(d_seq.ptr(), in.seq_bytes, in.seq_total);
         DBuf<u64> d_seq_begin(n);
         copy_h2d(d_seq_begin.ptr(), in.seq_begin, (u64)n * 8);
-#ifndef AC_EMU
-        AC_HIP_CHECK(hipEventRecord(e2, 0));
-#endif
+        meter.begin();      // the copy kernel alone: seconds_copy
         launch_full((n_bases + MERGE_COPY_WAVE_BYTES - 1) / MERGE_COPY_WAVE_BYTES * 64, MergeCopyFunctor{d_member_seq_off.ptr(), d_members.ptr(), nm, n_bases, d_seq.ptr(), d_seq_begin.ptr(), d_len.ptr(), d_out.ptr()});
-        launched++;
-#ifndef AC_EMU
-        AC_HIP_CHECK(hipEventRecord(e3, 0));
-#endif
+        meter.end();
         out->seq.resize(n_bases);
         copy_d2h_async(out->seq.data(), d_out.ptr(), n_bases);
     }
     out->chains.resize(nc); out->members.resize(nm); out->chain_of.resize(n); out->fixed.resize(n); out->links.resize((size_t)h.n_links_after);
-    static_assert(sizeof(MergeLink) == sizeof(Link), "MergeLink and Link are one layout");
     copy_d2h_async(out->chains.data(), d_records.ptr(), nc * sizeof(MergeChainRecord));
     copy_d2h_async(out->members.data(), d_members.ptr(), nm * 4);
     copy_d2h_async(out->chain_of.data(), d_chain_of.ptr(), (u64)n * 4);
@@ -518,23 +483,7 @@ void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
         copy_d2h_async(out->fwd_positions.data(), d_fwd.ptr(), (u64)n * 4);
         copy_d2h_async(out->rev_positions.data(), d_rev.ptr(), (u64)n * 4);
     }
-    stream_sync();
-#ifndef AC_EMU
-    {
-        float ms = 0, ms_copy = 0;
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        if (with_seq && n_bases) AC_HIP_CHECK(hipEventElapsedTime(&ms_copy, e2, e3));
-        out->seconds_device = comp_seconds + 1e-3 * (double)ms + 1e-3 * (double)ms_copy;
-        out->seconds_copy = 1e-3 * (double)ms_copy;
-        (void)t0;
-    }
-    rt_counters().readbacks++;      // (the bulk copies and their one synchronisation: a host round trip like copy_d2h's)
-    out->launches = comp_launches + (rt_counters().launches - before.launches);
-    out->read_backs = comp_read_backs + (rt_counters().readbacks - before.readbacks);
-    (void)launched;
-#else
-    out->seconds_device = comp_seconds + (now_s() - t0);
-    out->launches = comp_launches + launched;
-    out->read_backs = comp_read_backs + 2;
-#endif
+    meter.sync_copies();
+    out->stats += meter.stats();
+    out->seconds_copy = meter.seconds(1);      // (0 where no sequence was copied)
 }

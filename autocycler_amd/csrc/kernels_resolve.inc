@@ -125,14 +125,7 @@ void path_distance_batch(const PathPool& pool, const std::vector<PathPair>& pair
     const size_t MAX_JOBS_PER_LAUNCH = (size_t)1 << 22;
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    // (events of this feature's own, not from the ring of device_rt.hpp: nothing here may recycle an event a build still holds)
-    hipEvent_t e0, e1;
-    AC_HIP_CHECK(hipEventCreate(&e0));
-    struct EvFree { hipEvent_t* a; hipEvent_t* b; ~EvFree() { if (a) (void)hipEventDestroy(*a); if (b) (void)hipEventDestroy(*b); } } evfree{&e0, nullptr};
-    AC_HIP_CHECK(hipEventCreate(&e1));
-    evfree.b = &e1;
-#endif
+    StepMeter meter;
     // the pool and the weight of every entry, once for all launches
     const u64 n_ent = pool.entries.size();
     std::vector<u32> hw(n_ent);
@@ -155,23 +148,12 @@ void path_distance_batch(const PathPool& pool, const std::vector<PathPair>& pair
         {
             DBuf<ResolveJobDev> d_jobs(nb); DBuf<u32> d_edge(n_edge + 1), d_dist(nb);
             copy_h2d(d_jobs.ptr(), jd.data(), nb * sizeof(ResolveJobDev));
-            const double t0 = now_s();
-#ifndef AC_EMU
-            flush_fills();
-            AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
+            meter.begin();
             launch_wave_kernel(resolve_distance_kernel, (nb + 3) / 4, 0, (const ResolveJobDev*)d_jobs.ptr(), (u32)nb, (const int32_t*)d_ent.ptr(),
                                (const u32*)d_w.ptr(), d_edge.ptr(), d_dist.ptr());
-#ifndef AC_EMU
-            AC_HIP_CHECK(hipEventRecord(e1, 0));
-            AC_HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0;
-            AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            if (st) st->seconds_device += 1e-3 * (double)ms;
-            (void)t0;
-#else
-            if (st) st->seconds_device += now_s() - t0;
-#endif
+            meter.end();
+            const double seconds = meter.take();      // (waits for the kernel: the read-back below finds it done)
+            if (st) st->seconds_device += seconds;
             const std::vector<u32> hd = to_host(d_dist, nb);
             for (size_t q = q0; q < q1; q++) (*dist)[order[q]] = hd[q - q0];
             if (st) st->launches++;

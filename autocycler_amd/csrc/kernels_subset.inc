@@ -90,11 +90,10 @@ struct SubsetPairFunctor {
 struct SubsetLinkCountFunctor {
     const Link* links; u32 n; u32 words; const u64* bits; u64* kept; u64* first_bad;
     AC_D void operator()(u64 i) const {
-        const int64_t a = links[i].a, b = links[i].b;
-        const int64_t na = a < 0 ? -a : a, nb = b < 0 ? -b : b;
+        LinkEnds e;
         kept[i] = 0;
-        if (na == 0 || nb == 0 || na > (int64_t)n || nb > (int64_t)n) { atomic_min64(&first_bad[SUBSET_BAD_LINK], i); return; }
-        const u64* ra = bits + (u64)(na - 1) * words; const u64* rb = bits + (u64)(nb - 1) * words;
+        if (link_ends(links[i], n, nullptr, &e) != LINK_OK) { atomic_min64(&first_bad[SUBSET_BAD_LINK], i); return; }
+        const u64* ra = bits + (u64)e.ua * words; const u64* rb = bits + (u64)e.ub * words;
         u64 total = 0;
         for (u32 w = 0; w < words; w++) total += (u64)prim_popc64(ra[w] & rb[w]);
         kept[i] = total;
@@ -104,10 +103,9 @@ struct SubsetLinkCountFunctor {
 struct SubsetLinkKeyFunctor {
     const Link* links; u32 n; u32 words; const u64* bits; const u64* kept_off; u64 n_out; u64* key; u32* val;
     AC_D void operator()(u64 i) const {
-        const int64_t a = links[i].a, b = links[i].b;
-        const int64_t na = a < 0 ? -a : a, nb = b < 0 ? -b : b;
-        if (na == 0 || nb == 0 || na > (int64_t)n || nb > (int64_t)n) return;
-        const u64* ra = bits + (u64)(na - 1) * words; const u64* rb = bits + (u64)(nb - 1) * words;
+        LinkEnds e;
+        if (link_ends(links[i], n, nullptr, &e) != LINK_OK) return;
+        const u64* ra = bits + (u64)e.ua * words; const u64* rb = bits + (u64)e.ub * words;
         u64 at = kept_off[i];
         for (u32 w = 0; w < words; w++) {
             u64 m = ra[w] & rb[w];
@@ -140,8 +138,6 @@ struct SubsetOffsetsFunctor {
     }
 };
 
-static int subset_bit_width(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
-
 // the entries of kept sequences [first, first + count) of the plan, one copy per run of sequences that lie back to back in the caller's array
 static void subset_upload_entries(const SubsetPlan& plan, size_t first, size_t count, const int32_t* path, const u64* path_off, int32_t* d_path) {
     size_t i = first;
@@ -166,16 +162,10 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     if (nl >= 0xFFFFFFF0ULL) throw DeviceError("subsets: more than 2^32 links");
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    struct EvFree { hipEvent_t* e[4]; ~EvFree() { for (auto p : e) if (*p) (void)hipEventDestroy(*p); } } evfree{{&e0, &e1, &e2, &e3}};
-    AC_HIP_CHECK(hipEventCreate(&e0)); AC_HIP_CHECK(hipEventCreate(&e1)); AC_HIP_CHECK(hipEventCreate(&e2)); AC_HIP_CHECK(hipEventCreate(&e3));
-    const RtCounters before = rt_counters();
-#endif
-    u32 launched = 0;      // (the emulation's count: the device build reads the runtime's own counters)
+    StepMeter meter;
     const u32 words = (nc + 63) / 64;
     // (the links' sort always runs over all 16 bits a label can have: two passes whatever n_clusters, so that the launches follow the entry keys' width alone)
-    const int key_bits = subset_bit_width((u64)nc * n - 1), cluster_bits = 16;
+    const int key_bits = bit_width((u64)nc * n - 1), cluster_bits = 16;
 
     DBuf<int32_t> d_path(ne);
     DBuf<u64> d_kept_off(n_kept + 1);
@@ -198,28 +188,20 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     d_pair_start.fill_bytes(0); d_pair_key.fill_bytes(0);
     RadixScratch sort_keys;
     sort_keys.prepare(ne, key_bits);
-    auto sort_launches = [](size_t items, int bits) -> u32 { return items > 1 && bits > 0 ? 1u + (u32)std::min((bits + 7) / 8, 8) : 0u; };
 
-    const double t0 = now_s();
-#ifndef AC_EMU
-    flush_fills();
-    AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
-    launch(ne, SubsetKeyFunctor{d_path.ptr(), d_kept_off.ptr(), d_kept_label.ptr(), n_kept, n, p_alive, d_key.ptr(), d_val.ptr(), d_first_bad.ptr()}); launched++;
-    sort_pairs_u64_u32(d_key, d_val, ne, key_bits, 0, 0, &sort_keys); launched += sort_launches(ne, key_bits);
-    launch(ne, SubsetHeadFunctor{d_key.ptr(), d_head.ptr()}); launched++;
-    exclusive_scan_u32(d_head.ptr(), d_rank.ptr(), ne); launched++;
-    launch(ne, SubsetCompactFunctor{d_key.ptr(), d_head.ptr(), d_rank.ptr(), ne, d_pair_key.ptr(), d_pair_start.ptr(), d_counts.ptr()}); launched++;
+    meter.begin();
+    launch(ne, SubsetKeyFunctor{d_path.ptr(), d_kept_off.ptr(), d_kept_label.ptr(), n_kept, n, p_alive, d_key.ptr(), d_val.ptr(), d_first_bad.ptr()});
+    sort_pairs_u64_u32(d_key, d_val, ne, key_bits, 0, 0, &sort_keys);
+    launch(ne, SubsetHeadFunctor{d_key.ptr(), d_head.ptr()});
+    exclusive_scan_u32(d_head.ptr(), d_rank.ptr(), ne);
+    launch(ne, SubsetCompactFunctor{d_key.ptr(), d_head.ptr(), d_rank.ptr(), ne, d_pair_key.ptr(), d_pair_start.ptr(), d_counts.ptr()});
     launch(ne, SubsetPairFunctor{d_counts.ptr(), d_pair_key.ptr(), d_pair_start.ptr(), n, nc, words, d_len.ptr(), d_unit.ptr(), d_count.ptr(), d_len64.ptr(), d_bits.ptr()});
-    launched++;
-    exclusive_scan_u64(d_len64.ptr(), d_len_prefix.ptr(), ne + 1); launched++;
+    exclusive_scan_u64(d_len64.ptr(), d_len_prefix.ptr(), ne + 1);
     if (nl) {
-        launch(nl, SubsetLinkCountFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept.ptr(), d_first_bad.ptr()}); launched++;
-        exclusive_scan_u64(d_link_kept.ptr(), d_link_kept_off.ptr(), nl + 1); launched++;
+        launch(nl, SubsetLinkCountFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept.ptr(), d_first_bad.ptr()});
+        exclusive_scan_u64(d_link_kept.ptr(), d_link_kept_off.ptr(), nl + 1);
     }
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e1, 0));
-#endif
+    meter.end();
     // the header: errors, the pairs and the kept links — what sizes the second half and the bulk copy
     SubsetCounts h; u64 first_bad[3] = {~0ULL, ~0ULL, ~0ULL}; u64 n_out = 0;
     {
@@ -241,48 +223,26 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     DBuf<u64> d_link_key(n_out);
     DBuf<u32> d_link_val(n_out);
     DBuf<Link> d_links_out(n_out);
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e2, 0));
-#endif
+    meter.begin();
     if (n_out) {
-        launch(nl, SubsetLinkKeyFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept_off.ptr(), n_out, d_link_key.ptr(), d_link_val.ptr()}); launched++;
-        sort_pairs_u64_u32(d_link_key, d_link_val, n_out, 32 + cluster_bits, 0, 32); launched += sort_launches(n_out, cluster_bits);
-        launch(n_out, SubsetLinkDecodeFunctor{d_link_key.ptr(), d_links.ptr(), nl, d_links_out.ptr()}); launched++;
+        launch(nl, SubsetLinkKeyFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept_off.ptr(), n_out, d_link_key.ptr(), d_link_val.ptr()});
+        sort_pairs_u64_u32(d_link_key, d_link_val, n_out, 32 + cluster_bits, 0, 32);
+        launch(n_out, SubsetLinkDecodeFunctor{d_link_key.ptr(), d_links.ptr(), nl, d_links_out.ptr()});
     }
     launch((u64)nc + 1, SubsetOffsetsFunctor{d_counts.ptr(), d_pair_key.ptr(), d_len_prefix.ptr(), n, d_link_key.ptr(), n_out, d_unit_off.ptr(), d_length_at.ptr(),
                                              d_link_off.ptr()});
-    launched++;
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e3, 0));
-#endif
+    meter.end();
     const size_t c1 = (size_t)nc + 1;
     out->unitig_off.resize(c1); out->length_at.resize(c1); out->link_off.resize(c1);
     out->unitigs.resize((size_t)np); out->positions.resize((size_t)np); out->links.resize((size_t)n_out);
-    static_assert(sizeof(SubsetLink) == sizeof(Link), "SubsetLink and Link are one layout");
     copy_d2h_async(out->unitig_off.data(), d_unit_off.ptr(), c1 * 8);
     copy_d2h_async(out->length_at.data(), d_length_at.ptr(), c1 * 8);
     copy_d2h_async(out->link_off.data(), d_link_off.ptr(), c1 * 8);
     copy_d2h_async(out->unitigs.data(), d_unit.ptr(), np * 4);
     copy_d2h_async(out->positions.data(), d_count.ptr(), np * 4);
     copy_d2h_async(out->links.data(), d_links_out.ptr(), n_out * sizeof(Link));
-    stream_sync();
-#ifndef AC_EMU
-    {
-        float ms_a = 0, ms_b = 0;
-        AC_HIP_CHECK(hipEventElapsedTime(&ms_a, e0, e1));
-        AC_HIP_CHECK(hipEventElapsedTime(&ms_b, e2, e3));
-        out->seconds_device = 1e-3 * ((double)ms_a + (double)ms_b);
-        (void)t0;
-    }
-    rt_counters().readbacks++;      // (the bulk copies and their one synchronisation: a host round trip like copy_d2h's)
-    out->launches = rt_counters().launches - before.launches;
-    out->read_backs = rt_counters().readbacks - before.readbacks;
-    (void)launched;
-#else
-    out->seconds_device = now_s() - t0;
-    out->launches = launched;
-    out->read_backs = 2;
-#endif
+    meter.sync_copies();
+    out->stats = meter.stats();
 }
 
 // ---- the paths of one cluster over the merged unitigs ------------------------------------------------------------------------------------------
@@ -373,13 +333,7 @@ void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out) {
     if (ne >= 0xFFFFFFF0ULL) throw DeviceError("merged paths: more than 2^32 path entries in the cluster");
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvFree { hipEvent_t* a; hipEvent_t* b; ~EvFree() { if (*a) (void)hipEventDestroy(*a); if (*b) (void)hipEventDestroy(*b); } } evfree{&e0, &e1};
-    AC_HIP_CHECK(hipEventCreate(&e0)); AC_HIP_CHECK(hipEventCreate(&e1));
-    const RtCounters before = rt_counters();
-#endif
-    u32 launched = 0;
+    StepMeter meter;
     std::vector<u64> seq_off(ns + 1);
     for (size_t i = 0; i <= ns; i++) seq_off[i] = plan.kept_off[in.kept_first + i] - base;
 
@@ -397,21 +351,15 @@ void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out) {
     d_pos_in.fill_bytes(0); d_strand_in.fill_bytes(0); d_flag.fill_bytes(0); d_len_old.fill_bytes(0); d_len_new.fill_bytes(0); d_first_bad.fill_bytes(0xFF); d_err.fill_bytes(0);
     const MergedPathsView view{n, d_chain_of.ptr(), d_pos_in.ptr(), d_strand_in.ptr(), d_chains.ptr(), n_chains};
 
-    const double t0 = now_s();
-#ifndef AC_EMU
-    flush_fills();
-    AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
-    if (nm) { launch(nm, MergedPathsMemberFunctor{d_members.ptr(), n, d_chain_of.ptr(), d_chains.ptr(), n_chains, d_pos_in.ptr(), d_strand_in.ptr(), d_err.ptr()}); launched++; }
-    launch(ne, MergedPathsFlagFunctor{d_path.ptr(), view, d_len.ptr(), d_flag.ptr(), d_entry.ptr(), d_len_old.ptr(), d_len_new.ptr()}); launched++;
-    exclusive_scan_u32(d_flag.ptr(), d_rank.ptr(), ne + 1); launched++;
-    exclusive_scan_u64(d_len_old.ptr(), d_old_prefix.ptr(), ne + 1); launched++;
-    exclusive_scan_u64(d_len_new.ptr(), d_new_prefix.ptr(), ne + 1); launched++;
-    launch((u64)ns + 1, MergedPathsSeqFunctor{d_path.ptr(), view, d_seq_off.ptr(), ns, d_rank.ptr(), d_old_prefix.ptr(), d_new_prefix.ptr(), d_new_off.ptr(), d_first_bad.ptr()}); launched++;
-    launch(ne, MergedPathsScatterFunctor{d_flag.ptr(), d_rank.ptr(), d_entry.ptr(), ne, d_out.ptr()}); launched++;
-#ifndef AC_EMU
-    AC_HIP_CHECK(hipEventRecord(e1, 0));
-#endif
+    meter.begin();
+    if (nm) launch(nm, MergedPathsMemberFunctor{d_members.ptr(), n, d_chain_of.ptr(), d_chains.ptr(), n_chains, d_pos_in.ptr(), d_strand_in.ptr(), d_err.ptr()});
+    launch(ne, MergedPathsFlagFunctor{d_path.ptr(), view, d_len.ptr(), d_flag.ptr(), d_entry.ptr(), d_len_old.ptr(), d_len_new.ptr()});
+    exclusive_scan_u32(d_flag.ptr(), d_rank.ptr(), ne + 1);
+    exclusive_scan_u64(d_len_old.ptr(), d_old_prefix.ptr(), ne + 1);
+    exclusive_scan_u64(d_len_new.ptr(), d_new_prefix.ptr(), ne + 1);
+    launch((u64)ns + 1, MergedPathsSeqFunctor{d_path.ptr(), view, d_seq_off.ptr(), ns, d_rank.ptr(), d_old_prefix.ptr(), d_new_prefix.ptr(), d_new_off.ptr(), d_first_bad.ptr()});
+    launch(ne, MergedPathsScatterFunctor{d_flag.ptr(), d_rank.ptr(), d_entry.ptr(), ne, d_out.ptr()});
+    meter.end();
     u32 total = 0, err[2] = {0, 0}; u64 first_bad[3] = {~0ULL, ~0ULL, ~0ULL};
     {
         ReadBatch rb;
@@ -431,22 +379,7 @@ void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out) {
     out->entries.resize(total); out->path_off.resize(ns + 1);
     copy_d2h_async(out->entries.data(), d_out.ptr(), (u64)total * 4);
     copy_d2h_async(out->path_off.data(), d_new_off.ptr(), (ns + 1) * 8);
-    stream_sync();
+    meter.sync_copies();
     out->entries_before = ne;
-#ifndef AC_EMU
-    {
-        float ms = 0;
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        out->seconds_device = 1e-3 * (double)ms;
-        (void)t0;
-    }
-    rt_counters().readbacks++;
-    out->launches = rt_counters().launches - before.launches;
-    out->read_backs = rt_counters().readbacks - before.readbacks;
-    (void)launched;
-#else
-    out->seconds_device = now_s() - t0;
-    out->launches = launched;
-    out->read_backs = 2;
-#endif
+    out->stats = meter.stats();
 }

@@ -174,11 +174,7 @@ void overlap_alignment_batch(const std::vector<AlignJob>& jobs, const uint32_t* 
     const u64 budget = knobs().trim_batch_bytes;
     Arena& arena = Arena::device();
     arena.reset();
-#ifndef AC_EMU
-    hipEvent_t e0, e1;
-    AC_HIP_CHECK(hipEventCreate(&e0)); AC_HIP_CHECK(hipEventCreate(&e1));
-    struct EvFree { hipEvent_t a, b; ~EvFree() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evfree{e0, e1};
-#endif
+    StepMeter meter;
     for (size_t q0 = 0; q0 < nj;) {
         // the jobs of this launch
         size_t q1 = q0; u64 bit_words = 0, n_in = 0, n_edge = 0, n_piece = 0;
@@ -207,26 +203,15 @@ void overlap_alignment_batch(const std::vector<AlignJob>& jobs, const uint32_t* 
             copy_h2d(d_jobs.ptr(), jd.data(), nb * sizeof(TrimJobDev));
             copy_h2d(d_a.ptr(), ha.data(), n_in * 4); copy_h2d(d_b.ptr(), hb.data(), n_in * 4);
             copy_h2d(d_wa.ptr(), hwa.data(), n_in * 4); copy_h2d(d_wb.ptr(), hwb.data(), n_in * 4);
-            const double t0 = now_s();
-#ifndef AC_EMU
-            flush_fills();
-            AC_HIP_CHECK(hipEventRecord(e0, 0));
-#endif
+            meter.begin();
             launch_wave_kernel(trim_fill_kernel, nb, 0, (const TrimJobDev*)d_jobs.ptr(), (const int32_t*)d_a.ptr(), (const int32_t*)d_b.ptr(),
                                (const u32*)d_wa.ptr(), (const u32*)d_wb.ptr(), d_bits.ptr(), d_edge.ptr());
             launch_wave_kernel_sized(trim_trace_kernel, nb, 64u, 0, (const TrimJobDev*)d_jobs.ptr(), (const int32_t*)d_a.ptr(), (const int32_t*)d_b.ptr(),
                                      (const u32*)d_wa.ptr(), (const u32*)d_wb.ptr(), (const u64*)d_bits.ptr(), (const int64_t*)d_edge.ptr(), d_pieces.ptr(),
                                      d_hdr.ptr());
-#ifndef AC_EMU
-            AC_HIP_CHECK(hipEventRecord(e1, 0));
-            AC_HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0;
-            AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            if (st) st->seconds_device += 1e-3 * (double)ms;
-            (void)t0;
-#else
-            if (st) st->seconds_device += now_s() - t0;
-#endif
+            meter.end();
+            const double seconds = meter.take();      // (waits for the two kernels: the read-backs below find them done)
+            if (st) st->seconds_device += seconds;
             const std::vector<TrimHeader> hdr = to_host(d_hdr, nb);
             for (size_t q = q0; q < q1; q++) {
                 const TrimHeader& h = hdr[q - q0];

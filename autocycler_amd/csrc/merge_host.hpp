@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "graph_types.hpp"
+
 namespace ac {
 
 // ac_merge_chain, field for field (the device writes members, length, member_off, seq_off and loop; merge_finish the rest)
@@ -15,7 +17,6 @@ struct MergeChainRecord {
     double depth;
     uint8_t type, loop;
 };
-struct MergeLink { int32_t a, b; };      // ac_link
 enum MergeFixedFlag { MERGE_FIXED_START = 1, MERGE_FIXED_END = 2 };
 enum MergeUnitigType { MERGE_TYPE_OTHER = 0, MERGE_TYPE_ANCHOR = 1, MERGE_TYPE_CONSENTIG = 2, MERGE_TYPE_BRIDGE = 3 };
 static const uint32_t MERGE_NOT_MERGED = 0xFFFFFFFFu;
@@ -27,14 +28,14 @@ struct MergeResult {
     std::vector<uint32_t> chain_of;           // n_unitigs; MERGE_NOT_MERGED
     std::vector<uint8_t> fixed;               // n_unitigs; MergeFixedFlag bits
     std::vector<uint8_t> seq;                 // merged sequences, addressed by seq_off (empty: none asked for)
-    std::vector<MergeLink> links;             // the link set after the merge, ascending by (a, b)
+    std::vector<Link> links;                  // the link set after the merge, ascending by (a, b)
     std::vector<uint32_t> fwd_positions, rev_positions;      // the histogram of a handle's path entries (empty: the caller's own counts)
     // filled by merge_finish
     uint32_t alive = 0, merged_unitigs = 0, unitigs_after = 0;
     uint64_t bases_copied = 0;
     // filled by the device driver
-    uint32_t launches = 0, read_backs = 0;
-    double seconds_device = 0, seconds_copy = 0;      // seconds_copy: the sequence kernel alone
+    StepStats stats;              // (the components' analysis inside it included)
+    double seconds_copy = 0;      // of stats.seconds_device: the sequence kernel alone
 };
 
 // The seeds of get_fixed_unitig_starts_and_ends (:198-208): seed[u] gets MERGE_FIXED_START / MERGE_FIXED_END from the first and last entry

@@ -317,31 +317,29 @@ struct RbReadFunctor {
 };
 void random_access_ceilings(double* cas_gops, double* read_gops, u64 table_slots) {
     *cas_gops = 0; *read_gops = 0;
-#ifndef AC_EMU
+#ifndef AC_EMU      // (a property of the device: the emulation has none to report, and 400 M functor calls to spend on it)
     Arena::device().reset();
     u64 cap = 1ULL << 24;
     while (cap < table_slots && cap < (1ULL << 30)) cap <<= 1;      // (at most an 8 GB table: the rate is flat from 4 GB on)
     const u64 n_cas = std::min<u64>(cap / 2, 48000000), n_read = 48000000;
     DBuf<u64> slots(cap), sink(1);
-    hipEvent_t e0, e1;
-    AC_HIP_CHECK(hipEventCreate(&e0)); AC_HIP_CHECK(hipEventCreate(&e1));
-    float best_cas = 1e9f, best_read = 1e9f;
+    StepMeter meter;
+    double best_cas = 1e6, best_read = 1e6;      // seconds
     for (int rep = 0; rep < 4; rep++) {
         slots.fill_bytes(0xFF);
         stream_sync();
-        AC_HIP_CHECK(hipEventRecord(e0, 0));
+        meter.begin();
         launch(n_cas, RbClaimFunctor{slots.ptr(), cap - 1, (u64)rep * 77});
-        AC_HIP_CHECK(hipEventRecord(e1, 0)); AC_HIP_CHECK(hipEventSynchronize(e1));
-        float ms; AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        if (rep && ms < best_cas) best_cas = ms;
-        AC_HIP_CHECK(hipEventRecord(e0, 0));
+        meter.end();
+        const double s_cas = meter.take();
+        if (rep && s_cas < best_cas) best_cas = s_cas;
+        meter.begin();
         launch(n_read, RbReadFunctor{slots.ptr(), cap - 1, (u64)rep * 131, sink.ptr()});
-        AC_HIP_CHECK(hipEventRecord(e1, 0)); AC_HIP_CHECK(hipEventSynchronize(e1));
-        AC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        if (rep && ms < best_read) best_read = ms;
+        meter.end();
+        const double s_read = meter.take();
+        if (rep && s_read < best_read) best_read = s_read;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *cas_gops = n_cas / (best_cas * 1e-3) / 1e9;
-    *read_gops = n_read / (best_read * 1e-3) / 1e9;
+    *cas_gops = n_cas / best_cas / 1e9;
+    *read_gops = n_read / best_read / 1e9;
 #endif
 }

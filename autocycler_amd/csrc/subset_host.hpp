@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "graph_types.hpp"
+
 namespace ac {
 
 // ac_subset_cluster, field for field
@@ -14,7 +16,6 @@ struct SubsetClusterRecord {
     uint32_t seqs, unitigs;             // kept sequences; alive unitigs
     uint64_t entries, links, length;    // path entries of the kept sequences; kept links; total length of the alive unitigs
 };
-struct SubsetLink { int32_t a, b; };      // ac_link
 
 // The kept sequences in the order their entries are laid out for the device: cluster after cluster, ascending index inside a cluster.
 struct SubsetPlan {
@@ -31,14 +32,13 @@ struct SubsetResult {
     std::vector<uint32_t> unitigs, positions;            // alive unitig numbers ascending per cluster; entries of the kept paths on each
     std::vector<uint64_t> length_at;                     // n_clusters + 1: total length of the alive unitigs of the clusters before
     std::vector<uint64_t> link_off;                      // n_clusters + 1
-    std::vector<SubsetLink> links;                       // in the input's order per cluster
+    std::vector<Link> links;                             // in the input's order per cluster
     std::vector<uint64_t> seq_off;                       // n_clusters + 1
     std::vector<uint32_t> seq_index;                     // kept sequences ascending per cluster
     std::vector<uint64_t> ends_off;                      // n_clusters + 1: in pairs
     std::vector<int32_t> path_ends;                      // first, last signed entry of every non-empty kept path
     uint64_t kept_entries = 0;
-    uint32_t launches = 0, read_backs = 0;
-    double seconds_device = 0;
+    StepStats stats;      // filled by the device driver
 };
 
 // Checks n_clusters, the labels and the offsets; fills the plan and, in the result, the sequence lists and path ends.  Throws
@@ -63,8 +63,7 @@ struct MergedPathsResult {
     std::vector<uint64_t> path_off;       // seq_index.size() + 1
     std::vector<int32_t> entries;
     uint64_t entries_before = 0;
-    uint32_t launches = 0, read_backs = 0;
-    double seconds_device = 0;
+    StepStats stats;      // filled by the device driver
 };
 std::string merged_paths_inside_message(uint32_t seq, bool begins, int32_t entry, uint32_t chain_number);
 std::string merged_paths_length_message(uint32_t seq);

@@ -71,7 +71,7 @@ int main() {
         SubsetResult x = r;
         x.unitig_off = {0, 3, 3, 4}; x.unitigs = {1, 2, 3, 5}; x.positions = {1, 2, 2, 1};
         x.length_at = {0, 10 + 20 + 30, 60, 110};
-        x.link_off = {0, 2, 2, 2}; x.links = {SubsetLink{1, 2}, SubsetLink{-2, -1}};
+        x.link_off = {0, 2, 2, 2}; x.links = {Link{1, 2}, Link{-2, -1}};
         return x;
     };
     {
