@@ -143,6 +143,18 @@ class MergedPathsSummary(C.Structure):      # ac_merged_paths_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class FinishedUnitig(C.Structure):      # ac_finished_unitig
+    _fields_ = [("number", C.c_uint32), ("source", C.c_uint32), ("length", C.c_uint64), ("seq_off", C.c_uint64), ("depth", C.c_double), ("type", C.c_uint8)]
+
+
+class FinishedSummary(C.Structure):      # ac_finished_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "unitigs", "renumbered", "launches", "read_backs")] + \
+               [(n, C.c_uint64) for n in ("links", "path_entries", "bases", "tie_items")] + [("seconds_device", C.c_double), ("seconds_gather", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -201,7 +213,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -338,6 +350,19 @@ def load_library(path=None):
     lib.ac_merged_paths_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(MergedPathsSummary), C.c_size_t]
     lib.ac_merged_paths_free.argtypes = [C.c_void_p]
     lib.ac_merged_paths_free.restype = None
+    lib.ac_merge_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_subsets_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_finished_unitigs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(FinishedUnitig)), C.POINTER(C.c_uint32)]
+    lib.ac_finished_sequences.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+    lib.ac_finished_new_of_old.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
+    lib.ac_finished_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Link)), C.POINTER(C.c_uint64)]
+    lib.ac_finished_paths.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_int32))]
+    lib.ac_finished_summary_get_sized.restype = C.c_size_t
+    lib.ac_finished_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(FinishedSummary), C.c_size_t]
+    lib.ac_finished_free.argtypes = [C.c_void_p]
+    lib.ac_finished_free.restype = None
+    lib.ac_finished_gfa_string.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_finished_to_graph.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.ac_cluster_max_seqs.restype = C.c_uint32
     lib.ac_cluster_max_seqs.argtypes = []
     lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -909,8 +934,8 @@ def graph_merge_plan(graph, use_paths=True, with_sequences=True, device=0, lib_p
 
 
 def merge_plan_from_links(n_unitigs, links, unitig_len, alive=None, path_ends=None, depth=None, fwd_positions=None, rev_positions=None, unitig_type=None,
-                          sequences=None, device=0, lib_path=None):
-    """ac_merge_plan_from_links: the same on plain arrays.  links: (a, b) pairs of signed unitig numbers, a set closed under reverse
+                          sequences=None, device=0, lib_path=None, keep=False):
+    """ac_merge_plan_from_links: the same on plain arrays (keep: the plan's handle stays open for merge_finish, until close()).  links: (a, b) pairs of signed unitig numbers, a set closed under reverse
     complement; path_ends: (first, last) signed entries per sequence; fwd_positions / rev_positions: position counts per unitig;
     unitig_type: MergePlan.OTHER / ANCHOR / CONSENTIG / BRIDGE per unitig; sequences: one bytes object per unitig (forward strand), or a
     tuple (all bytes as a uint8 array, the first byte of every unitig as a uint64 array)."""
@@ -942,15 +967,16 @@ def merge_plan_from_links(n_unitigs, links, unitig_len, alive=None, path_ends=No
     h = C.c_void_p()
     _check(lib, lib.ac_merge_plan_from_links(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(pe), pe.shape[0], ptr(dp), ptr(fw), ptr(rv), ptr(ty),
                                              ptr(sb), ptr(sg), device, C.byref(h)))
-    return MergePlan(lib, h, n_unitigs)
+    return MergePlan(lib, h, n_unitigs, keep=keep)
 
 
 class MergedPaths:
     """What ac_subsets_merged_paths found, copied out of the handle: seq_index (the cluster's kept sequences, ascending), path_off, entries
     (sequence seq_index[i] = entries[path_off[i] : path_off[i + 1]], merged unitigs under their chain numbers), summary."""
 
-    def __init__(self, lib, h):
+    def __init__(self, lib, h, keep=False):
         import numpy as np
+        self._lib, self._h = lib, None      # (keep: the handle lives on for Subsets.finish / merge_finish, until close())
         try:
             sp, sn, op, ep = C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_int32)()
             _check(lib, lib.ac_merged_paths_get(h, C.byref(sp), C.byref(sn), C.byref(op), C.byref(ep)))
@@ -960,8 +986,22 @@ class MergedPaths:
             sm = MergedPathsSummary()
             assert lib.ac_merged_paths_summary_get_sized(h, C.byref(sm), C.sizeof(MergedPathsSummary)) == C.sizeof(MergedPathsSummary) == sm.size
             self.summary = sm.as_dict()
+            if keep:
+                self._h, h = h, None
         finally:
-            lib.ac_merged_paths_free(h)
+            if h is not None:
+                lib.ac_merged_paths_free(h)
+
+    def close(self):
+        if self._h:
+            self._lib.ac_merged_paths_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def paths(self):
         """{sequence index: list of signed numbers}"""
@@ -1080,13 +1120,159 @@ class Subsets:
                                                           int(bool(with_sequences)), device, C.byref(h)))
         return MergePlan(self._lib, h, self.n_unitigs, keep=True)
 
-    def merged_paths(self, c, plan, device=0):
-        """ac_subsets_merged_paths: the paths of cluster c's sequences over the merged unitigs of `plan` (from merge_plan(c))"""
+    def merged_paths(self, c, plan, device=0, keep=False):
+        """ac_subsets_merged_paths: the paths of cluster c's sequences over the merged unitigs of `plan` (from merge_plan(c)).  keep: the
+        handle stays open for finish()"""
         if getattr(plan, "_h", None) is None:
             raise AutocyclerError("merged_paths: the plan must come from Subsets.merge_plan and still be open")
         h = C.c_void_p()
         _check(self._lib, self._lib.ac_subsets_merged_paths(self._h, c, plan._h, device, C.byref(h)))
-        return MergedPaths(self._lib, h)
+        return MergedPaths(self._lib, h, keep=keep)
+
+    def finish(self, c, plan, merged_paths=None, renumber=False, sequences=None, device=0):
+        """ac_subsets_finish: cluster c's graph after the merge of `plan` (from merge_plan(c)) as a Finished.  merged_paths: from
+        merged_paths(c, plan, keep=True) for the P lines, or None; sequences as for merge_plan."""
+        import numpy as np
+        if getattr(plan, "_h", None) is None:
+            raise AutocyclerError("finish: the plan must come from Subsets.merge_plan and still be open")
+        if merged_paths is not None and getattr(merged_paths, "_h", None) is None:
+            raise AutocyclerError("finish: the merged paths must come from Subsets.merged_paths(..., keep=True) and still be open")
+        sb = sg = None
+        if sequences is not None:
+            sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), np.ascontiguousarray(sequences[1], dtype=np.uint64)
+            if sg.shape != (self.n_unitigs,):
+                raise AutocyclerError(f"sequences[1]: one entry per unitig expected ({self.n_unitigs}), got shape {sg.shape}")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_subsets_finish(self._h, c, plan._h, merged_paths._h if merged_paths is not None else None,
+                                                      sb.ctypes.data if sb is not None else None, sg.ctypes.data if sg is not None else None,
+                                                      1 if renumber else 0, device, C.byref(h)))
+        return Finished(self._lib, h)
+
+
+class Finished:
+    """Owning handle of an ac_finished: a merge plan applied.  The arrays are copied out on construction; the handle stays for gfa() and
+    to_graph() until close().
+    unitigs        structured array in S-line order: number (as printed), source (an old number, or n_unitigs + 1 + chain index), length,
+                   seq_off, depth, type
+    sequences      the bytes in that order: unitig i = sequences[seq_off : seq_off + length]
+    new_of_old     the printed number of every old number and chain number (n_unitigs + chains entries), 0 = gone
+    links          (m, 2) int32 in L-line order (get_links_for_gfa after the merge), printed numbers
+    path_seq, path_off, path_entries   the P lines (those of the MergedPaths it was made with), printed numbers
+    summary        dict (unitigs, renumbered, launches, read_backs, links, path_entries, bases, tie_items, seconds_device, seconds_gather)"""
+
+    def __init__(self, lib, h):
+        import numpy as np
+        self._lib, self._h = lib, h
+        dt = np.dtype([("number", "<u4"), ("source", "<u4"), ("length", "<u8"), ("seq_off", "<u8"), ("depth", "<f8"), ("type", "u1")], align=True)
+        assert dt.itemsize == C.sizeof(FinishedUnitig)
+        up, un = C.POINTER(FinishedUnitig)(), C.c_uint32()
+        _check(lib, lib.ac_finished_unitigs(h, C.byref(up), C.byref(un)))
+        self.unitigs = _take(up, un.value, dt)
+        sp, sn = C.POINTER(C.c_uint8)(), C.c_uint64()
+        _check(lib, lib.ac_finished_sequences(h, C.byref(sp), C.byref(sn)))
+        self.sequences = _take(sp, sn.value, "u1")
+        np_, nn = C.POINTER(C.c_uint32)(), C.c_uint64()
+        _check(lib, lib.ac_finished_new_of_old(h, C.byref(np_), C.byref(nn)))
+        self.new_of_old = _take(np_, nn.value, "<u4")
+        lp, ln = C.POINTER(Link)(), C.c_uint64()
+        _check(lib, lib.ac_finished_links(h, C.byref(lp), C.byref(ln)))
+        self.links = _take(lp, 2 * ln.value, "<i4").reshape(-1, 2)
+        qp, qn, op, ep = C.POINTER(C.c_uint32)(), C.c_uint32(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_int32)()
+        _check(lib, lib.ac_finished_paths(h, C.byref(qp), C.byref(qn), C.byref(op), C.byref(ep)))
+        self.path_seq = _take(qp, qn.value, "<u4")
+        self.path_off = _take(op, qn.value + 1, "<u8")
+        self.path_entries = _take(ep, int(self.path_off[-1]), "<i4")
+        sm = FinishedSummary()
+        assert lib.ac_finished_summary_get_sized(h, C.byref(sm), C.sizeof(FinishedSummary)) == C.sizeof(FinishedSummary) == sm.size
+        self.summary = sm.as_dict()
+
+    def close(self):
+        if self._h:
+            self._lib.ac_finished_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def unitig_sequences(self):
+        b = self.sequences.tobytes()
+        return [b[int(u["seq_off"]):int(u["seq_off"]) + int(u["length"])] for u in self.unitigs]
+
+    def paths(self):
+        """{sequence index: list of signed printed numbers}"""
+        off, e = self.path_off.tolist(), self.path_entries.tolist()
+        return {int(s): e[off[i]:off[i + 1]] for i, s in enumerate(self.path_seq.tolist())}
+
+    def _meta(self, seq_ids, seq_lengths, filenames, headers, cluster_tags=None):
+        import numpy as np
+        n = len(self.path_seq)
+        for what, v in (("seq_ids", seq_ids), ("seq_lengths", seq_lengths), ("filenames", filenames), ("headers", headers)):
+            if len(v) != n:
+                raise AutocyclerError(f"{what}: one entry per P line expected ({n}), got {len(v)}")
+        ids, lens = np.ascontiguousarray(seq_ids, dtype=np.uint16), np.ascontiguousarray(seq_lengths, dtype=np.uint32)
+        fns = (C.c_char_p * max(n, 1))(*[x.encode() for x in filenames])
+        hds = (C.c_char_p * max(n, 1))(*[x.encode() for x in headers])
+        tags = np.ascontiguousarray(cluster_tags, dtype=np.uint32) if cluster_tags is not None else None
+        if tags is not None and tags.shape != (n,):
+            raise AutocyclerError(f"cluster_tags: one entry per P line expected ({n}), got shape {tags.shape}")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        return (ptr(ids), ptr(lens), fns, hds, ptr(tags)), (ids, lens, fns, hds, tags)
+
+    def gfa(self, k, seq_ids=(), seq_lengths=(), filenames=(), headers=(), cluster_tags=None, use_other_colour=False):
+        """ac_finished_gfa_string: save_gfa's text (bytes).  One id / length / filename / header (and cluster tag) per P line."""
+        args, keep = self._meta(seq_ids, seq_lengths, filenames, headers, cluster_tags)
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.ac_finished_gfa_string(self._h, k, *args, 1 if use_other_colour else 0, C.byref(out), C.byref(n)))
+        text = C.string_at(out.value, n.value)
+        self._lib.ac_string_free(out)
+        return text
+
+    def to_graph(self, k, seq_ids=(), seq_lengths=(), filenames=(), headers=()):
+        """ac_finished_to_graph: an ordinary Graph (renumber = 1 and every type Other only)"""
+        args, keep = self._meta(seq_ids, seq_lengths, filenames, headers)
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_finished_to_graph(self._h, k, *args[:4], C.byref(h)))
+        return Graph(self._lib, h, self._lib.ac_graph_seq_count(h))
+
+
+def merge_finish(plan, n_unitigs, links, unitig_len, alive=None, depth=None, unitig_type=None, sequences=None, paths=None, renumber=False, device=0, lib_path=None):
+    """ac_merge_finish: the graph after the merge.  plan: a MergePlan whose handle is open (Subsets.merge_plan's); links, unitig_len, alive,
+    depth, unitig_type: the arrays the plan was made from, the links in list order; sequences: (all bytes as a uint8 array, the first byte of
+    every unitig as a uint64 array), or one bytes object per unitig; paths: a MergedPaths made with keep_handle, or None."""
+    import numpy as np
+    lib = load_library(lib_path)
+    if getattr(plan, "_h", None) is None:
+        raise AutocyclerError("merge_finish: the plan's handle must be open (merge_plan_from_links(..., keep=True) or Subsets.merge_plan)")
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+
+    def per_unitig(values, dtype, what):
+        if values is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+        if a.shape != (n_unitigs,):
+            raise AutocyclerError(f"{what}: one entry per unitig expected ({n_unitigs}), got shape {a.shape}")
+        return a
+    ln, dp, ty = per_unitig(unitig_len, np.uint32, "unitig_len"), per_unitig(depth, np.float64, "depth"), per_unitig(unitig_type, np.uint8, "unitig_type")
+    al = _bytes_per_unitig(alive, n_unitigs, "alive")
+    sb = sg = None
+    if isinstance(sequences, tuple):
+        sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), per_unitig(sequences[1], np.uint64, "sequences[1]")
+    elif sequences is not None:
+        if len(sequences) != n_unitigs:
+            raise AutocyclerError(f"sequences: one entry per unitig expected ({n_unitigs}), got {len(sequences)}")
+        sg = np.zeros(max(n_unitigs, 1), dtype=np.uint64)
+        sg[1:n_unitigs] = np.cumsum([len(x) for x in sequences[:-1]], dtype=np.uint64) if n_unitigs > 1 else []
+        sb = np.frombuffer(b"".join(bytes(x) for x in sequences) + b"\0", dtype=np.uint8)
+    if ln is not None and ln.size == 0:
+        ln = np.zeros(1, dtype=np.uint32)      # (n_unitigs == 0: the entry still wants a pointer)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_merge_finish(plan._h, n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(dp), ptr(ty), ptr(sb), ptr(sg),
+                                    paths._h if paths is not None else None, 1 if renumber else 0, device, C.byref(h)))
+    return Finished(lib, h)
 
 
 def graph_subsets(graph, cluster_of_seq, n_clusters=None, device=0, lib_path=None):

@@ -614,6 +614,160 @@ size_t ac_merged_paths_summary_get_sized(const ac_merged_paths* p, ac_merged_pat
 }
 void ac_merged_paths_free(ac_merged_paths* p) { delete p; }
 
+// ---- a finished graph: a merge plan applied.  The S-line order with renumber_unitigs, the gather, the L lines and the relabelling on the device
+// (kernels_finish.inc); the checks and save_gfa's text on the host (finish_host.cpp, gfa_writer.cpp).  Read-only ----
+struct ac_finished {
+    FinishResult r;
+    ac_finished_summary summary;
+};
+static_assert(sizeof(ac_finished_unitig) == sizeof(FinishedUnitigRecord) && offsetof(ac_finished_unitig, length) == offsetof(FinishedUnitigRecord, length) &&
+              offsetof(ac_finished_unitig, seq_off) == offsetof(FinishedUnitigRecord, seq_off) && offsetof(ac_finished_unitig, depth) == offsetof(FinishedUnitigRecord, depth) &&
+              offsetof(ac_finished_unitig, type) == offsetof(FinishedUnitigRecord, type), "ac_finished_unitig and FinishedUnitigRecord are one layout");
+static void finish_run(const ac_merge* plan, uint32_t n, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const double* depth,
+                       const uint8_t* type, const uint8_t* seq_bytes, const uint64_t* seq_begin, uint64_t seq_total, const ac_merged_paths* paths, int renumber, int device,
+                       ac_finished** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!plan) throw DeviceError("null pointer: plan");
+    if (n_links && !links) throw DeviceError("null pointer: n_links > 0 without links");
+    FinishArrays a;
+    a.n_unitigs = n; a.unitig_len = unitig_len; a.alive = alive; a.depth = depth; a.type = type; a.seq_bytes = seq_bytes; a.seq_begin = seq_begin; a.n_links = n_links;
+    const uint64_t after = finish_check_inputs(plan->r, a, renumber != 0);
+    auto h = std::make_unique<ac_finished>();
+    if (after == 0) {      // (nothing to launch: no device is asked for)
+        finish_empty(&h->r, renumber != 0);
+        h->r.new_of_old.assign((size_t)n + plan->r.chains.size(), 0);
+        if (paths && !paths->r.entries.empty()) throw DeviceError(finish_bad_path_entry_message(0, paths->r.entries[0]));
+    } else {
+        FinishInput in;
+        in.n_unitigs = n; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.alive = alive; in.depth = depth; in.type = type;
+        in.seq_bytes = seq_bytes; in.seq_begin = seq_begin; in.seq_total = seq_total; in.plan = &plan->r; in.renumber = renumber != 0; in.unitigs_after = after;
+        if (paths) { in.path = paths->r.entries.data(); in.n_path = paths->r.entries.size(); }
+        DeviceCall call(device);
+        merge_finish_device(in, &h->r);
+        finish_check_result(h->r, plan->r, after);
+    }
+    h->r.n_unitigs = n; h->r.n_chains = (uint32_t)plan->r.chains.size(); h->r.renumbered = renumber != 0;
+    if (paths) { h->r.path_seq = paths->r.seq_index; h->r.path_off = paths->r.path_off; }
+    else h->r.path_off.assign(1, 0);
+    ac_finished_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.unitigs = (uint32_t)h->r.unitigs.size(); sm.renumbered = renumber != 0; sm.launches = h->r.stats.launches;
+    sm.read_backs = h->r.stats.read_backs; sm.links = h->r.links.size(); sm.path_entries = h->r.path_entries.size(); sm.bases = h->r.seq.size();
+    sm.tie_items = h->r.tie_items; sm.seconds_device = h->r.stats.seconds_device; sm.seconds_gather = h->r.seconds_gather;
+    *out = h.release();
+}
+int ac_merge_finish(const ac_merge* plan, uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const double* depth,
+                    const uint8_t* type, const uint8_t* seq_bytes, const uint64_t* seq_begin, const ac_merged_paths* paths, int renumber, int device, ac_finished** out) {
+    return guarded([&] {
+        uint64_t seq_total = 0;
+        if (seq_bytes && seq_begin && unitig_len)
+            for (uint32_t u = 0; u < n_unitigs; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + unitig_len[u]);
+        finish_run(plan, n_unitigs, links, n_links, unitig_len, alive, depth, type, seq_bytes, seq_begin, seq_total, paths, renumber, device, out);
+    });
+}
+int ac_subsets_finish(const ac_subsets* s, uint32_t cluster, const ac_merge* plan, const ac_merged_paths* merged_paths, const uint8_t* seq_bytes, const uint64_t* seq_begin,
+                      int renumber, int device, ac_finished** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!s || !plan) throw DeviceError("null pointer");
+        if ((seq_bytes == nullptr) != (seq_begin == nullptr)) throw DeviceError("seq_bytes and seq_begin: both or neither");
+        subset_check_cluster(s->r, cluster);
+        if (plan->cluster != cluster)
+            throw DeviceError("finish: the plan was made for cluster " + std::to_string(plan->cluster) + ", not for cluster " + std::to_string(cluster));
+        const uint32_t n = s->r.n_unitigs;
+        std::vector<uint8_t> alive(n);
+        std::vector<double> depth(n);
+        subset_dense(s->r, cluster, alive.data(), nullptr, nullptr, depth.data());
+        uint64_t seq_total = 0;
+        if (!seq_bytes && s->graph && s->graph->g.seq_block.p && s->graph->g.seq_begin) {
+            seq_bytes = (const uint8_t*)s->graph->g.seq_block.p; seq_begin = s->graph->g.seq_begin; seq_total = s->graph->g.seq_block.bytes;
+        } else if (seq_bytes)
+            for (uint32_t u = 0; u < n; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + s->unitig_len[u]);
+        const uint64_t l0 = s->r.link_off[cluster - 1], l1 = s->r.link_off[cluster];
+        finish_run(plan, n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), depth.data(), nullptr, seq_bytes, seq_begin, seq_total, merged_paths,
+                   renumber, device, out);
+    });
+}
+int ac_finished_unitigs(const ac_finished* f, const ac_finished_unitig** unitigs, uint32_t* n) {
+    return guarded([&] {
+        if (!f || !unitigs || !n) throw DeviceError("null pointer");
+        *unitigs = (const ac_finished_unitig*)f->r.unitigs.data(); *n = (uint32_t)f->r.unitigs.size();
+    });
+}
+int ac_finished_sequences(const ac_finished* f, const uint8_t** bytes, uint64_t* n) {
+    return guarded([&] {
+        if (!f || !bytes || !n) throw DeviceError("null pointer");
+        *bytes = f->r.seq.data(); *n = f->r.seq.size();
+    });
+}
+int ac_finished_new_of_old(const ac_finished* f, const uint32_t** printed, uint64_t* n) {
+    return guarded([&] {
+        if (!f || !printed || !n) throw DeviceError("null pointer");
+        *printed = f->r.new_of_old.data(); *n = f->r.new_of_old.size();
+    });
+}
+int ac_finished_links(const ac_finished* f, const ac_link** links, uint64_t* n) {
+    return guarded([&] {
+        if (!f || !links || !n) throw DeviceError("null pointer");
+        *links = (const ac_link*)f->r.links.data(); *n = f->r.links.size();
+    });
+}
+int ac_finished_paths(const ac_finished* f, const uint32_t** seq_index, uint32_t* n_seqs, const uint64_t** path_off, const int32_t** entries) {
+    return guarded([&] {
+        if (!f || !seq_index || !n_seqs || !path_off || !entries) throw DeviceError("null pointer");
+        *seq_index = f->r.path_seq.data(); *n_seqs = (uint32_t)f->r.path_seq.size(); *path_off = f->r.path_off.data(); *entries = f->r.path_entries.data();
+    });
+}
+size_t ac_finished_summary_get_sized(const ac_finished* f, ac_finished_summary* out, size_t out_size) {
+    if (f && out) memcpy(out, &f->summary, std::min(out_size, sizeof(ac_finished_summary)));
+    return sizeof(ac_finished_summary);
+}
+void ac_finished_free(ac_finished* f) { delete f; }
+static std::vector<FinishSeqMeta> finish_meta(const ac_finished* f, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames,
+                                              const char* const* headers, const uint32_t* cluster_tags) {
+    const size_t np = f->r.path_seq.size();
+    if (np && (!seq_ids || !seq_lengths || !filenames || !headers)) throw DeviceError("null pointer: the P lines want ids, lengths, filenames and headers");
+    std::vector<FinishSeqMeta> meta(np);
+    for (size_t i = 0; i < np; i++) {
+        if (!filenames[i] || !headers[i]) throw DeviceError("null pointer: filename or header of P line " + std::to_string(i));
+        meta[i] = FinishSeqMeta{seq_ids[i], seq_lengths[i], filenames[i], headers[i], cluster_tags ? cluster_tags[i] : 0u};
+    }
+    return meta;
+}
+int ac_finished_gfa_string(const ac_finished* f, uint32_t k, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames, const char* const* headers,
+                           const uint32_t* cluster_tags, int use_other_colour, char** out, uint64_t* len) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!f) throw DeviceError("null pointer");
+        const std::string s = finish_gfa_string(f->r, k, finish_meta(f, seq_ids, seq_lengths, filenames, headers, cluster_tags), use_other_colour != 0);
+        char* p = (char*)malloc(s.size() + 1);
+        if (!p) throw DeviceError("out of memory");
+        memcpy(p, s.c_str(), s.size() + 1);
+        *out = p;
+        if (len) *len = s.size();
+    });
+}
+int ac_finished_to_graph(const ac_finished* f, uint32_t k, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames, const char* const* headers,
+                         ac_graph** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!f) throw DeviceError("null pointer");
+        if (!f->r.renumbered) throw DeviceError("finish: a graph handle numbers its unitigs 1, 2, 3, ...: make the finished graph with renumber = 1");
+        for (const FinishedUnitigRecord& u : f->r.unitigs)
+            if (u.type != MERGE_TYPE_OTHER) throw DeviceError("finish: unitig " + std::to_string(u.number) + " is not of type Other: a graph handle holds no types");
+        const std::string s = finish_gfa_string(f->r, k, finish_meta(f, seq_ids, seq_lengths, filenames, headers, nullptr), false);
+        auto h = std::make_unique<ac_graph>();
+        std::vector<SeqMeta> meta;
+        load_gfa(s.data(), s.size(), &h->g, &meta);
+        for (auto& m : meta) { h->seq_ids.push_back(m.id); h->seq_lens.push_back(m.length); h->filenames.push_back(m.filename); h->headers.push_back(m.contig_header); }
+        *out = h.release();
+    });
+}
+
 // ---- `autocycler cluster`: the UPGMA tree.  The merge loop on the device (kernels_cluster.inc), the tree and what the reference derives
 // from it on the host (cluster_host.cpp); the QC verdicts, scores and refinement further down.  Writing the clusters stays with the caller ----
 struct ac_cluster_tree {

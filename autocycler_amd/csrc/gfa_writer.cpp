@@ -1,5 +1,6 @@
 #include "gfa_writer.hpp"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
@@ -40,7 +41,7 @@ struct Out {
 
 // Rust's {:.2} of a depth.  Depths of a compress graph are whole numbers (occurrence counts): those skip snprintf.
 static inline void put_depth(Out& o, double d) {
-    if (d >= 0 && d < 9e15 && d == (double)(uint64_t)d) { o.u64((uint64_t)d); AC_LIT(o, ".00"); return; }
+    if (d >= 0 && d < 9e15 && d == (double)(uint64_t)d && !std::signbit(d)) { o.u64((uint64_t)d); AC_LIT(o, ".00"); return; }      // (-0.0 prints its sign: "-0.00")
     char buf[64]; const int len = snprintf(buf, sizeof buf, "%.2f", d);
     o.lit(buf, (size_t)len);
 }
@@ -85,6 +86,46 @@ std::string gfa_string(const FinalGraph& g, const std::vector<SeqMeta>& seqs, in
             o.ch('\n');   // cluster is 0 in compress output: no CL:i tag (unitig_graph.rs:357)
         }
     }
+    return out;
+}
+
+std::string gfa_string_explicit(uint32_t k, const std::vector<GfaSegmentView>& segments, const Link* links, uint64_t n_links, const std::vector<GfaPathView>& paths,
+                                bool use_other_colour) {
+    std::string out;
+    size_t est = 64 + (size_t)n_links * 32;
+    for (const GfaSegmentView& s : segments) est += (size_t)s.length + 48;
+    for (const GfaPathView& p : paths) est += (size_t)p.n_entries * 10 + 256;
+    out.reserve(est);
+    out += "H\tVN:Z:1.0\tKM:i:"; put_u64(out, k); out.push_back('\n');
+    Out o(out);
+    for (const GfaSegmentView& s : segments) {
+        AC_LIT(o, "S\t"); o.u64(s.number); o.ch('\t'); o.lit(s.seq, (size_t)s.length); AC_LIT(o, "\tDP:f:"); put_depth(o, s.depth);
+        switch (s.type) {      // colour_tag
+            case 2: AC_LIT(o, "\tCL:Z:steelblue"); break;
+            case 1: AC_LIT(o, "\tCL:Z:forestgreen"); break;
+            case 3: AC_LIT(o, "\tCL:Z:pink"); break;
+            default: if (use_other_colour) AC_LIT(o, "\tCL:Z:orangered"); break;
+        }
+        o.ch('\n');
+    }
+    for (uint64_t li = 0; li < n_links; li++) {
+        const Link& l = links[li];
+        AC_LIT(o, "L\t"); o.u64(l.na()); if (l.a_fwd()) AC_LIT(o, "\t+\t"); else AC_LIT(o, "\t-\t"); o.u64(l.nb());
+        if (l.b_fwd()) AC_LIT(o, "\t+\t0M\n"); else AC_LIT(o, "\t-\t0M\n");
+    }
+    for (const GfaPathView& p : paths) {
+        AC_LIT(o, "P\t"); o.u64(p.id); o.ch('\t');
+        for (uint64_t i = 0; i < p.n_entries; i++) {
+            if (i) o.ch(',');
+            const int32_t v = p.entries[i];
+            o.u64((uint64_t)(v < 0 ? -(int64_t)v : (int64_t)v)); o.ch(v < 0 ? '-' : '+');
+        }
+        AC_LIT(o, "\t*\tLN:i:"); o.u64(p.length);
+        AC_LIT(o, "\tFN:Z:"); o.str(*p.filename); AC_LIT(o, "\tHD:Z:"); o.str(*p.header);
+        if (p.cluster > 0) { AC_LIT(o, "\tCL:i:"); o.u64(p.cluster); }
+        o.ch('\n');
+    }
+    o.flush();
     return out;
 }
 

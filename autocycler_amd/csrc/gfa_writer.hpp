@@ -14,4 +14,10 @@ std::string gfa_string(const FinalGraph& g, const std::vector<SeqMeta>& seqs, in
 void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs);
 void decompress_sequence(const FinalGraph& g, size_t seq_index, char* out);      // out: LN bytes
 std::vector<std::string> gfa_chunks(const FinalGraph& g, const std::vector<SeqMeta>& seqs, int threads);
+// The same text for a graph whose segments carry explicit numbers and types (a graph after merge_linear_paths): the S lines print `number`
+// and colour_tag (unitig.rs:174-182), a P line whose cluster is above 0 ends in CL:i:<cluster> (unitig_graph.rs:357).
+struct GfaSegmentView { uint32_t number; const char* seq; uint64_t length; double depth; uint8_t type; };      // type: 0 Other, 1 Anchor, 2 Consentig, 3 Bridge
+struct GfaPathView { uint16_t id; const int32_t* entries; uint64_t n_entries; uint32_t length; const std::string* filename; const std::string* header; uint32_t cluster; };
+std::string gfa_string_explicit(uint32_t k, const std::vector<GfaSegmentView>& segments, const Link* links, uint64_t n_links, const std::vector<GfaPathView>& paths,
+                                bool use_other_colour);
 }  // namespace ac

@@ -17,6 +17,7 @@
 #include "components_host.hpp"
 #include "merge_host.hpp"
 #include "subset_host.hpp"
+#include "finish_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -243,6 +244,14 @@ struct MergedPathsInput {
     const SubsetPlan* plan = nullptr; size_t kept_first = 0, kept_count = 0; const MergeResult* merge = nullptr;
 };
 void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out);
+// A finished graph (kernels_finish.inc): a merge plan applied to the arrays it was made from — the S-line order (renumbered or not), the
+// gathered sequences, the L lines in get_links_for_gfa order and the relabelled path entries.  unitigs_after: finish_check_inputs'.
+struct FinishInput {
+    uint32_t n_unitigs = 0; const Link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const uint8_t* alive = nullptr;
+    const double* depth = nullptr; const uint8_t* type = nullptr; const uint8_t* seq_bytes = nullptr; const uint64_t* seq_begin = nullptr; uint64_t seq_total = 0;
+    const MergeResult* plan = nullptr; const int32_t* path = nullptr; uint64_t n_path = 0; bool renumber = false; uint64_t unitigs_after = 0;
+};
+void merge_finish_device(const FinishInput& in, FinishResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

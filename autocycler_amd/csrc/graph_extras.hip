@@ -1,7 +1,8 @@
 // The neighbouring rows of SURVEY.md §8 (f): device end repair and pairwise contig distances (neighbours.inc), the round-trip verifier
 // and device decompress (kernels_verify.inc); trim's path-overlap alignment (kernels_trim.inc); resolve's path distances (kernels_resolve.inc);
 // cluster's UPGMA merge loop (kernels_cluster.inc) and the QC of its clusters (kernels_cluster_qc.inc); connected components and topology
-// (kernels_components.inc); the linear-path merge plan (kernels_merge.inc); sequence subsets and the paths over merged unitigs (kernels_subset.inc).
+// (kernels_components.inc); the linear-path merge plan (kernels_merge.inc); sequence subsets and the paths over merged unitigs (kernels_subset.inc);
+// the finished graph after a merge: order, renumbering, L lines (kernels_finish.inc).
 #include "graph_impl.hpp"
 
 namespace ac {
@@ -15,5 +16,6 @@ namespace ac {
 #include "kernels_components.inc" // ac_graph_components / ac_components_from_links: connected_components, circular loops, link_count, topology (f-9)
 #include "kernels_merge.inc"   // ac_graph_merge_plan / ac_merge_plan_from_links: merge_linear_paths as a plan, with its products (f-10)
 #include "kernels_subset.inc"  // ac_graph_subsets / ac_subsets_from_paths / ac_subsets_merged_paths: what each cluster of sequences keeps (f-11)
+#include "kernels_finish.inc"  // ac_merge_finish / ac_subsets_finish: the S-line order, renumber_unitigs, the L and P lines after a merge (f-12)
 
 }  // namespace ac

@@ -354,7 +354,7 @@ void merge_plan_device(const MergePlanInput& in, MergeResult* out) {
     *out = MergeResult();
     const u32 n = in.n_unitigs;
     const u64 nl = in.n_links;
-    out->n_unitigs = n;
+    out->n_unitigs = n; out->links_in = nl;
     if (n > 0x7FFFFFFEu) throw DeviceError("merge plan: more unitigs than a signed unitig number can name");
     if (nl >= 0xFFFFFFF0ULL) throw DeviceError("merge plan: more than 2^32 links");
     if (n == 0) {

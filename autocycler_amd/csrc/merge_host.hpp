@@ -34,6 +34,7 @@ struct MergeResult {
     uint32_t alive = 0, merged_unitigs = 0, unitigs_after = 0;
     uint64_t bases_copied = 0;
     // filled by the device driver
+    uint64_t links_in = 0;        // how many links the plan was made from (a finished graph wants the same ones)
     StepStats stats;              // (the components' analysis inside it included)
     double seconds_copy = 0;      // of stats.seconds_device: the sequence kernel alone
 };

@@ -682,6 +682,68 @@ int ac_merged_paths_get(const ac_merged_paths*, const uint32_t** seq_index, uint
 size_t ac_merged_paths_summary_get_sized(const ac_merged_paths*, ac_merged_paths_summary* out, size_t out_size);
 void ac_merged_paths_free(ac_merged_paths*);
 
+/* A finished graph: a merge plan applied — what the reference holds after merge_linear_paths and, optionally, renumber_unitigs
+ * (unitig_graph.rs:295-315), up to the text of save_gfa (:317-360).  Read-only: made from a plan plus the arrays the plan was made from.
+ * Additions of ABI generation 13, found by name; AC_ABI_VERSION stays 13.
+ *   S lines   renumber = 0: graph.unitigs after merge_path's push and retain — the unmerged alive unitigs in ascending old number, then the
+ *             merged unitigs in chain order; numbers stay as they are (old numbers; n_unitigs + 1 + i for chain i).
+ *             renumber = 1: a stable sort of that order by length descending, forward sequence bytewise ascending, depth descending
+ *             (partial_cmp; -0.0 == 0.0); ties keep the order above; the printed number is the place + 1.
+ *   L lines   get_links_for_gfa order (:333-350) after merge_path's list pushes (graph_simplification.rs:410-485) and delete_dangling_links:
+ *             per unitig in S order its forward_next, then its reverse_next.  The input's link order matters: every source's entries must be
+ *             in list order, as ac_links, ac_subsets_links and the L lines of a GFA are.
+ *   P lines   the entries of an ac_merged_paths under the printed numbers (paths = NULL: none).
+ * On the device: the order (three radix sorts — depth, the first 8 bytes, length — then an exact merge sort of what they leave open, a
+ * wavefront per comparison), the gather of the sequences in final order, the link order (one key per input link, a radix sort) and both
+ * relabellings.  The number of launches follows the key widths and log2 of the unitigs alone.
+ * Errors (return 1, ac_last_error), never faults: a plan over another n_unitigs; n_links that differs from the plan's; an alive mask that
+ * leaves another number of unitigs than the plan; renumber = 1 with a NaN depth (the unitig is named: the reference's comparator is no total
+ * order there); missing sequences (seq_bytes / seq_begin NULL while unmerged unitigs have bases, or a plan made without sequences); links
+ * that touch the inside of a chain; a path entry that names no unitig after the merge; NULL plan, out or unitig_len. */
+typedef struct ac_finished ac_finished;
+typedef struct {
+    uint32_t number;         /* as printed */
+    uint32_t source;         /* where it comes from: an old number, or n_unitigs + 1 + chain index */
+    uint64_t length;
+    uint64_t seq_off;        /* first byte in ac_finished_sequences */
+    double   depth;
+    uint8_t  type;           /* AC_UNITIG_* */
+} ac_finished_unitig;
+typedef struct {
+    uint32_t size;           /* the library's sizeof(ac_finished_summary) */
+    uint32_t unitigs, renumbered;
+    uint32_t launches, read_backs;
+    uint64_t links, path_entries, bases;
+    uint64_t tie_items;      /* unitigs whose place the radix keys left open: longer than 8 bases, same length and first 8 bytes as another */
+    double seconds_device;   /* the kernels of the call, by device events */
+    double seconds_gather;   /* of those, the kernel that gathers the sequences */
+} ac_finished_summary;
+int ac_merge_finish(const ac_merge* plan, uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len,
+        const uint8_t* alive /* or NULL */, const double* depth /* or NULL = 0 */, const uint8_t* type /* or NULL = Other */,
+        const uint8_t* seq_bytes, const uint64_t* seq_begin, const ac_merged_paths* paths /* or NULL */, int renumber, int device,
+        ac_finished** out);
+/* The same for cluster c of an ac_subsets: its kept links, alive mask and depths (the position counts), every type Other; plan and
+ * merged_paths (or NULL) from ac_subsets_merge_plan / ac_subsets_merged_paths of that cluster.  seq_bytes / seq_begin: NULL, NULL on a
+ * handle-made object takes the handle's sequences. */
+int ac_subsets_finish(const ac_subsets*, uint32_t cluster, const ac_merge* plan, const ac_merged_paths* merged_paths, const uint8_t* seq_bytes,
+        const uint64_t* seq_begin, int renumber, int device, ac_finished** out);
+/* The arrays belong to the object. */
+int ac_finished_unitigs(const ac_finished*, const ac_finished_unitig** unitigs, uint32_t* n);
+int ac_finished_sequences(const ac_finished*, const uint8_t** bytes, uint64_t* n);
+int ac_finished_new_of_old(const ac_finished*, const uint32_t** printed /* n_unitigs + chains; 0 = gone */, uint64_t* n);
+int ac_finished_links(const ac_finished*, const ac_link** links, uint64_t* n);
+int ac_finished_paths(const ac_finished*, const uint32_t** seq_index, uint32_t* n_seqs, const uint64_t** path_off /* n_seqs + 1 */, const int32_t** entries);
+size_t ac_finished_summary_get_sized(const ac_finished*, ac_finished_summary* out, size_t out_size);
+void ac_finished_free(ac_finished*);
+/* save_gfa's text: the printed numbers, DP:f:{:.2}, colour_tag's CL:Z: (unitig.rs:174-182), CL:i:<cluster> on a P line whose tag is above 0
+ * (unitig_graph.rs:357).  One seq_id / seq_length / filename / header (and cluster tag, or cluster_tags = NULL) per P line.  *out is
+ * malloc'ed and 0-terminated (ac_string_free); *len, when given, its length. */
+int ac_finished_gfa_string(const ac_finished*, uint32_t k, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames,
+        const char* const* headers, const uint32_t* cluster_tags, int use_other_colour, char** out, uint64_t* len);
+/* An ordinary graph handle, as ac_graph_from_gfa makes, of a finished graph made with renumber = 1 whose unitigs are all of type Other. */
+int ac_finished_to_graph(const ac_finished*, uint32_t k, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames,
+        const char* const* headers, ac_graph** out);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -985,7 +1047,10 @@ const char* ac_version(void);
  *      unchanged): ac_graph_subsets, ac_subsets_from_paths, ac_subsets_records, ac_subsets_unitigs, ac_subsets_links, ac_subsets_seqs,
  *      ac_subsets_path_ends, ac_subsets_dense, ac_subsets_summary_get_sized, ac_subsets_free, ac_subsets_components, ac_subsets_merge_plan,
  *      ac_subsets_merged_paths, ac_merged_paths_get, ac_merged_paths_summary_get_sized, ac_merged_paths_free with ac_subset_cluster,
- *      ac_subsets_summary and ac_merged_paths_summary. */
+ *      ac_subsets_summary and ac_merged_paths_summary; then, still generation 13 and found by name: ac_merge_finish, ac_subsets_finish,
+ *      ac_finished_unitigs, ac_finished_sequences, ac_finished_new_of_old, ac_finished_links, ac_finished_paths,
+ *      ac_finished_summary_get_sized, ac_finished_free, ac_finished_gfa_string, ac_finished_to_graph with ac_finished_unitig and
+ *      ac_finished_summary. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
