@@ -155,6 +155,15 @@ class FinishedSummary(C.Structure):      # ac_finished_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class AppliedSummary(C.Structure):      # ac_applied_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "bridges_applied", "direct_links", "launches", "launches_components", "read_backs")] + \
+               [(n, C.c_uint64) for n in ("removed_no_anchor", "removed_zero_depth", "links_in", "links_out", "bases_copied")] + \
+               [("seconds_device", C.c_double), ("seconds_copy", C.c_double), ("seconds_components", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -213,7 +222,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -367,6 +376,22 @@ def load_library(path=None):
     lib.ac_cluster_max_seqs.argtypes = []
     lib.ac_cluster_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.ac_cluster_tree_from_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_apply_bridges.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_graph_resolve_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_applied_unitigs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_double)),
+                                       C.POINTER(C.POINTER(C.c_uint8))]
+    lib.ac_applied_bridge_of.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+    lib.ac_applied_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Link)), C.POINTER(C.c_uint64)]
+    lib.ac_applied_bridge_sequences.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    lib.ac_applied_summary_get_sized.restype = C.c_size_t
+    lib.ac_applied_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(AppliedSummary), C.c_size_t]
+    lib.ac_applied_free.argtypes = [C.c_void_p]
+    lib.ac_applied_free.restype = None
+    lib.ac_applied_merge_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_applied_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_applied_gfa_string.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_resolve_graphs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
     lib.ac_cluster_tree_from_nodes.argtypes = [C.POINTER(ClusterNode), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ac_cluster_nodes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterNode)), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     lib.ac_cluster_merges.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterMerge)), C.POINTER(C.c_uint32)]
@@ -555,6 +580,28 @@ class Graph:
         h = C.c_void_p()
         _check(self._lib, self._lib.ac_resolve_bridges(self._h, device, C.byref(h)))
         return _resolve_result(self._lib, h)
+
+    def resolve_apply(self, which="unique", device=0):
+        """ac_graph_resolve_apply on the bridges ac_resolve_bridges finds on this graph: apply_bridges with reduce_depths and the two removals.
+        which: "unique" (the bridges that do not conflict: the first pass) or "kept" (those cull_ambiguity kept: the final pass).  An Applied."""
+        if which not in ("unique", "kept"):
+            raise AutocyclerError('which: "unique" or "kept"')
+        r, h = C.c_void_p(), C.c_void_p()
+        _check(self._lib, self._lib.ac_resolve_bridges(self._h, device, C.byref(r)))
+        try:
+            _check(self._lib, self._lib.ac_graph_resolve_apply(self._h, r, Applied.UNIQUE if which == "unique" else Applied.KEPT, device, C.byref(h)))
+        finally:
+            self._lib.ac_resolve_free(r)
+        return Applied(self._lib, h)
+
+    def resolve_graphs(self, device=0):
+        """ac_resolve_graphs: resolve.rs:44-67 on this graph -> (3_bridged.gfa, 4_merged.gfa, 5_final.gfa as bytes, cull count)"""
+        outs, n = [C.c_void_p(), C.c_void_p(), C.c_void_p()], C.c_uint32()
+        _check(self._lib, self._lib.ac_resolve_graphs(self._h, device, C.byref(outs[0]), C.byref(outs[1]), C.byref(outs[2]), C.byref(n)))
+        texts = [C.string_at(o.value) for o in outs]
+        for o in outs:
+            self._lib.ac_string_free(o)
+        return texts[0], texts[1], texts[2], n.value
 
     def default_tip_names(self):
         """Sequence::string_for_newick (sequence.rs:77-87) per sequence: "{id}__{filename}__{contig_name}__{length}_bp", the contig
@@ -1273,6 +1320,133 @@ def merge_finish(plan, n_unitigs, links, unitig_len, alive=None, depth=None, uni
     _check(lib, lib.ac_merge_finish(plan._h, n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(dp), ptr(ty), ptr(sb), ptr(sg),
                                     paths._h if paths is not None else None, 1 if renumber else 0, device, C.byref(h)))
     return Finished(lib, h)
+
+
+class Applied:
+    """Owning handle of an ac_applied: a graph after apply_bridges, reduce_depths and the two removals (resolve.rs:223-282).  The arrays are
+    copied out on construction; the handle stays for merge_plan(), finish() and gfa() until close().
+    n_unitigs, n_total   the caller's n; n + the bridge unitigs (unitig n_unitigs + 1 + i was made from bridge bridge_of[i])
+    len, alive, depth, type   per unitig 1 .. n_total (type: MergePlan.OTHER / ANCHOR / BRIDGE)
+    links          (m, 2) int32 in get_links_for_gfa order: the alive originals ascending, then the bridge unitigs
+    bridge_sequences, bridge_seq_off   the bridge unitigs' bytes: unitig i = bridge_sequences[bridge_seq_off[i] : bridge_seq_off[i + 1]]
+    summary        dict (bridges_applied, direct_links, launches, launches_components, read_backs, removed_no_anchor, removed_zero_depth,
+                   links_in, links_out, bases_copied, seconds_device, seconds_copy, seconds_components)"""
+    UNIQUE, KEPT = 0, 1
+
+    def __init__(self, lib, h):
+        self._lib, self._h = lib, h
+        nt, lp, ap, dp, tp = C.c_uint32(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint8)()
+        _check(lib, lib.ac_applied_unitigs(h, C.byref(nt), C.byref(lp), C.byref(ap), C.byref(dp), C.byref(tp)))
+        self.n_total = nt.value
+        self.len, self.alive, self.depth, self.type = _take(lp, nt.value, "<u4"), _take(ap, nt.value, "u1"), _take(dp, nt.value, "<f8"), _take(tp, nt.value, "u1")
+        bp, bn = C.POINTER(C.c_uint32)(), C.c_uint32()
+        _check(lib, lib.ac_applied_bridge_of(h, C.byref(bp), C.byref(bn)))
+        self.bridge_of = _take(bp, bn.value, "<u4")
+        self.n_unitigs = self.n_total - bn.value
+        kp, kn = C.POINTER(Link)(), C.c_uint64()
+        _check(lib, lib.ac_applied_links(h, C.byref(kp), C.byref(kn)))
+        self.links = _take(kp, 2 * kn.value, "<i4").reshape(-1, 2)
+        sp, op, sn = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(lib, lib.ac_applied_bridge_sequences(h, C.byref(sp), C.byref(op), C.byref(sn)))
+        self.bridge_sequences = _take(sp, sn.value, "u1")
+        self.bridge_seq_off = _take(op, bn.value + 1, "<u8")
+        sm = AppliedSummary()
+        assert lib.ac_applied_summary_get_sized(h, C.byref(sm), C.sizeof(AppliedSummary)) == C.sizeof(AppliedSummary) == sm.size
+        self.summary = sm.as_dict()
+
+    def close(self):
+        if self._h:
+            self._lib.ac_applied_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def bridge_unitig_sequences(self):
+        b, off = self.bridge_sequences.tobytes(), self.bridge_seq_off.tolist()
+        return [b[off[i]:off[i + 1]] for i in range(len(off) - 1)] if len(b) else []
+
+    def merge_plan(self, with_sequences=True, device=0):
+        """ac_applied_merge_plan: merge_linear_paths(graph, &vec![]) after clear_positions; the plan's handle stays open for finish()"""
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_applied_merge_plan(self._h, int(bool(with_sequences)), device, C.byref(h)))
+        return MergePlan(self._lib, h, self.n_total, keep=True)
+
+    def finish(self, plan, renumber=True, device=0):
+        """ac_applied_finish: the graph after that merge (renumber: renumber_unitigs), a Finished"""
+        if getattr(plan, "_h", None) is None:
+            raise AutocyclerError("Applied.finish: the plan's handle must be open (Applied.merge_plan)")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_applied_finish(self._h, plan._h, 1 if renumber else 0, device, C.byref(h)))
+        return Finished(self._lib, h)
+
+    def gfa(self, k, use_other_colour=False):
+        """ac_applied_gfa_string: 3_bridged.gfa's text (bytes): the edited graph under its own numbers, no P lines"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.ac_applied_gfa_string(self._h, k, 1 if use_other_colour else 0, C.byref(out), C.byref(n)))
+        text = C.string_at(out.value, n.value)
+        self._lib.ac_string_free(out)
+        return text
+
+
+def apply_bridges(n_unitigs, links, unitig_len, anchors, bridges, apply="unique", bridge_depth=1.0, alive=None, depth=None, sequences=None, device=0, lib_path=None):
+    """ac_apply_bridges: apply_bridges with reduce_depths and the two removals on plain arrays.  links: (a, b) pairs of signed unitig numbers in
+    list order, a set closed under reverse complement; anchors: ascending unitig numbers; bridges: the dicts resolve_bridge_paths returns, in
+    its order (start, end, status, best_path, distinct_paths [(path, multiplicity)], conflicting, culled); apply: "unique" (not conflicting),
+    "kept" (not culled) or one truth value per bridge; sequences: one bytes object per unitig, or (uint8 array, uint64 first bytes)."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+
+    def per_unitig(values, dtype, what):
+        if values is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+        if a.shape != (n_unitigs,):
+            raise AutocyclerError(f"{what}: one entry per unitig expected ({n_unitigs}), got shape {a.shape}")
+        return a
+    ln, dp, al = per_unitig(unitig_len, np.uint32, "unitig_len"), per_unitig(depth, np.float64, "depth"), _bytes_per_unitig(alive, n_unitigs, "alive")
+    an = np.ascontiguousarray(np.asarray(anchors, dtype=np.uint32).reshape(-1))
+    sb = sg = None
+    if isinstance(sequences, tuple):
+        sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), per_unitig(sequences[1], np.uint64, "sequences[1]")
+    elif sequences is not None:
+        if len(sequences) != n_unitigs:
+            raise AutocyclerError(f"sequences: one entry per unitig expected ({n_unitigs}), got {len(sequences)}")
+        sg = np.zeros(max(n_unitigs, 1), dtype=np.uint64)
+        sg[1:n_unitigs] = np.cumsum([len(x) for x in sequences[:-1]], dtype=np.uint64) if n_unitigs > 1 else []
+        sb = np.frombuffer(b"".join(bytes(x) for x in sequences) + b"\0", dtype=np.uint8)
+    nb = len(bridges)
+    recs = (Bridge * max(nb, 1))()
+    best, dist, doff, mult = [], [], [0], []
+    for i, b in enumerate(bridges):
+        r = recs[i]
+        r.start, r.end, r.status, r.conflicting, r.culled = b["start"], b["end"], b.get("status", 0), int(b.get("conflicting", 0)), int(b.get("culled", 0))
+        bp = b.get("best_path") or []
+        r.best_off, r.best_len = len(best), len(bp)
+        best.extend(bp)
+        r.first_distinct, r.n_distinct = len(mult), len(b.get("distinct_paths", ()))
+        for path, m in b.get("distinct_paths", ()):
+            dist.extend(path); doff.append(len(dist)); mult.append(m)
+    if isinstance(apply, str):
+        if apply not in ("unique", "kept"):
+            raise AutocyclerError('apply: "unique", "kept" or one truth value per bridge')
+        flags = [not b.get("conflicting", 0) if apply == "unique" else not b.get("culled", 0) for b in bridges]
+    else:
+        flags = [bool(x) for x in apply]
+        if len(flags) != nb:
+            raise AutocyclerError(f"apply: one entry per bridge expected ({nb}), got {len(flags)}")
+    fl = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8).reshape(-1))
+    ba, da = np.asarray(best, dtype=np.int32), np.asarray(dist, dtype=np.int32)
+    oa, ma = np.asarray(doff, dtype=np.uint64), np.asarray(mult, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_apply_bridges(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(dp), ptr(an), an.shape[0], ptr(sb), ptr(sg), recs if nb else None, nb,
+                                     ptr(ba), ba.shape[0], ptr(da), oa.ctypes.data, ptr(ma), ma.shape[0], ptr(fl), float(bridge_depth), device, C.byref(h)))
+    return Applied(lib, h)
 
 
 def graph_subsets(graph, cluster_of_seq, n_clusters=None, device=0, lib_path=None):

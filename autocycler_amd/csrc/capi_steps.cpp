@@ -116,7 +116,7 @@ int ac_overlap_alignment(const int32_t* a, const int32_t* b, uint32_t n, const u
 uint32_t ac_trim_max_unitigs(void) { return trim_max_unitigs(); }
 
 // ---- `autocycler resolve`: anchors, bridges and their best paths.  The path distances on the device (kernels_resolve.inc), everything around
-// them on the host (resolve_host.cpp).  Applying the bridges to the graph stays with the caller ----
+// them on the host (resolve_host.cpp).  Applying the bridges to the graph: ac_graph_resolve_apply, further down ----
 struct ac_resolve {
     ResolveResult r;
     std::vector<ac_bridge> records;
@@ -238,7 +238,7 @@ uint32_t ac_resolve_max_path(void) { return resolve_max_path(); }
 void ac_resolve_free(ac_resolve* r) { delete r; }
 
 // ---- connected components and topology: the analysis on the device (kernels_components.inc), totals and the topology chain on the host
-// (components_host.cpp).  Read-only: the graph edits that rest on it stay with the caller ----
+// (components_host.cpp).  Read-only: of the graph edits that rest on it, resolve's removal of the anchorless components is ac_graph_resolve_apply ----
 struct ac_components {
     ComponentsResult r;
     ac_components_summary summary;
@@ -312,7 +312,7 @@ const char* ac_topology_name(uint32_t topology) { return components_topology_nam
 void ac_components_free(ac_components* c) { delete c; }
 
 // ---- the linear-path merge plan: chains, members, sequences and the link set after the merge on the device (kernels_merge.inc); the fixed
-// seeds, depths, types and totals on the host (merge_host.cpp).  Read-only: applying the plan to a graph stays with the caller ----
+// seeds, depths, types and totals on the host (merge_host.cpp).  Read-only: the plan is applied by ac_merge_finish, further down ----
 struct ac_merge {
     MergeResult r;
     ac_merge_summary summary;
@@ -765,6 +765,204 @@ int ac_finished_to_graph(const ac_finished* f, uint32_t k, const uint16_t* seq_i
         load_gfa(s.data(), s.size(), &h->g, &meta);
         for (auto& m : meta) { h->seq_ids.push_back(m.id); h->seq_lens.push_back(m.length); h->filenames.push_back(m.filename); h->headers.push_back(m.contig_header); }
         *out = h.release();
+    });
+}
+
+// ---- `autocycler resolve`, the edit: apply_bridges with reduce_depths and the two removals on the device (kernels_apply.inc); the checks on the
+// bridge records, the numbering and the text on the host (apply_host.cpp).  The composed entries hand the edited arrays to the merge plan and the
+// finished graph above; ac_resolve_graphs is resolve.rs:44-67 from a handle to the three texts ----
+struct ac_applied {
+    ApplyResult r;
+    ac_applied_summary summary;
+};
+static void apply_run(const ApplyInput& in, int device, ac_applied** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    ApplyPlan plan;
+    apply_prepare(in, &plan);
+    auto h = std::make_unique<ac_applied>();
+    if (in.n_unitigs == 0) {      // (nothing to launch: no device is asked for)
+        if (in.n_links) throw DeviceError(components_bad_link_message(0, in.links[0].a, in.links[0].b, 0));
+        apply_empty(&h->r);
+    } else {
+        DeviceCall call(device);
+        apply_bridges_device(in, plan, &h->r);
+    }
+    apply_finish(in, plan, &h->r);
+    ac_applied_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.bridges_applied = h->r.applied; sm.direct_links = h->r.direct; sm.launches_components = h->r.stats_components.launches;
+    sm.launches = h->r.stats.launches - h->r.stats_components.launches; sm.read_backs = h->r.stats.read_backs; sm.removed_no_anchor = h->r.removed_no_anchor;
+    sm.removed_zero_depth = h->r.removed_zero_depth; sm.links_in = h->r.links_in; sm.links_out = h->r.links.size(); sm.bases_copied = h->r.bases_copied;
+    sm.seconds_device = h->r.stats.seconds_device; sm.seconds_copy = h->r.seconds_copy; sm.seconds_components = h->r.stats_components.seconds_device;
+    *out = h.release();
+}
+static std::vector<ApplyBridgeIn> apply_bridge_records(const ac_bridge* bridges, uint32_t n) {
+    std::vector<ApplyBridgeIn> v(n);
+    for (uint32_t b = 0; b < n; b++)
+        v[b] = ApplyBridgeIn{bridges[b].start, bridges[b].end, bridges[b].best_off, bridges[b].first_distinct, bridges[b].best_len, bridges[b].n_distinct, bridges[b].status};
+    return v;
+}
+int ac_apply_bridges(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const double* depth,
+                     const uint32_t* anchors, uint32_t n_anchors, const uint8_t* seq_bytes, const uint64_t* seq_begin, const ac_bridge* bridges, uint32_t n_bridges,
+                     const int32_t* best_paths, uint64_t n_best, const int32_t* distinct_entries, const uint64_t* distinct_off, const uint32_t* multiplicity,
+                     uint64_t n_distinct_paths, const uint8_t* apply, double bridge_depth, int device, ac_applied** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (n_bridges && !bridges) throw DeviceError("null pointer: n_bridges > 0 without bridges");
+        const std::vector<ApplyBridgeIn> recs = apply_bridge_records(bridges, n_bridges);
+        ApplyInput in;
+        in.n_unitigs = n_unitigs; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.alive = alive; in.depth = depth;
+        in.anchors = anchors; in.n_anchors = n_anchors; in.seq_bytes = seq_bytes; in.seq_begin = seq_begin;
+        if (seq_bytes && seq_begin && unitig_len)
+            for (uint32_t u = 0; u < n_unitigs; u++) in.seq_total = std::max<uint64_t>(in.seq_total, seq_begin[u] + unitig_len[u]);
+        in.bridges = recs.data(); in.n_bridges = n_bridges; in.apply = apply; in.best = best_paths; in.n_best = n_best;
+        in.dist_entries = distinct_entries; in.dist_off = distinct_off; in.dist_mult = multiplicity; in.n_dist_paths = n_distinct_paths;
+        in.n_dist_entries = n_distinct_paths && distinct_off ? distinct_off[n_distinct_paths] : 0;
+        in.bridge_depth = bridge_depth;
+        apply_run(in, device, out);
+    });
+}
+static void apply_on_graph(const ac_graph* g, const ac_resolve* r, int which, int device, ac_applied** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!g || !r) throw DeviceError("null pointer");
+    if (which != AC_APPLY_UNIQUE && which != AC_APPLY_KEPT) throw DeviceError("apply bridges: which must be AC_APPLY_UNIQUE or AC_APPLY_KEPT");
+    if (!g->host_arrays) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+    const FinalGraph& f = g->g;
+    const std::vector<ApplyBridgeIn> recs = apply_bridge_records(r->records.data(), (uint32_t)r->records.size());
+    std::vector<uint8_t> apply(recs.size());
+    for (size_t b = 0; b < recs.size(); b++) apply[b] = which == AC_APPLY_UNIQUE ? !r->records[b].conflicting : !r->records[b].culled;
+    const bool seqs = f.seq_block.p && f.seq_begin;
+    ApplyInput in;
+    in.n_unitigs = f.n_unitigs; in.links = f.links; in.n_links = f.n_links; in.unitig_len = f.seq_len; in.depth = f.depth;
+    in.anchors = r->r.anchors.data(); in.n_anchors = (uint32_t)r->r.anchors.size();
+    in.seq_bytes = seqs ? (const uint8_t*)f.seq_block.p : nullptr; in.seq_begin = seqs ? f.seq_begin : nullptr; in.seq_total = seqs ? f.seq_block.bytes : 0;
+    in.bridges = recs.data(); in.n_bridges = (uint32_t)recs.size(); in.apply = apply.data(); in.best = r->r.best_pool.data(); in.n_best = r->r.best_pool.size();
+    in.dist_entries = r->r.distinct.entries.data(); in.dist_off = r->r.distinct.off.data(); in.dist_mult = r->r.multiplicity.data();
+    in.n_dist_paths = r->r.distinct.size(); in.n_dist_entries = r->r.distinct.entries.size();
+    in.bridge_depth = (double)g->seq_ids.size();      // sequences.len() as f64 (resolve.rs:47)
+    apply_run(in, device, out);
+}
+int ac_graph_resolve_apply(const ac_graph* g, const ac_resolve* r, int which, int device, ac_applied** out) {
+    return guarded([&] { apply_on_graph(g, r, which, device, out); });
+}
+int ac_applied_unitigs(const ac_applied* a, uint32_t* n_total, const uint32_t** len, const uint8_t** alive, const double** depth, const uint8_t** type) {
+    return guarded([&] {
+        if (!a || !n_total) throw DeviceError("null pointer");
+        *n_total = a->r.n_total;
+        if (len) *len = a->r.len.data();
+        if (alive) *alive = a->r.alive.data();
+        if (depth) *depth = a->r.depth.data();
+        if (type) *type = a->r.type.data();
+    });
+}
+int ac_applied_bridge_of(const ac_applied* a, const uint32_t** bridge, uint32_t* n) {
+    return guarded([&] {
+        if (!a || !bridge || !n) throw DeviceError("null pointer");
+        *bridge = a->r.bridge_of.data(); *n = (uint32_t)a->r.bridge_of.size();
+    });
+}
+int ac_applied_links(const ac_applied* a, const ac_link** links, uint64_t* n) {
+    return guarded([&] {
+        if (!a || !links || !n) throw DeviceError("null pointer");
+        *links = (const ac_link*)a->r.links.data(); *n = a->r.links.size();
+    });
+}
+int ac_applied_bridge_sequences(const ac_applied* a, const uint8_t** bytes, const uint64_t** off, uint64_t* n_bytes) {
+    return guarded([&] {
+        if (!a || !bytes || !off) throw DeviceError("null pointer");
+        *bytes = a->r.bridge_seq.data(); *off = a->r.bridge_seq_off.data();
+        if (n_bytes) *n_bytes = a->r.bridge_seq.size();
+    });
+}
+size_t ac_applied_summary_get_sized(const ac_applied* a, ac_applied_summary* out, size_t out_size) {
+    if (a && out) memcpy(out, &a->summary, std::min(out_size, sizeof(ac_applied_summary)));
+    return sizeof(ac_applied_summary);
+}
+void ac_applied_free(ac_applied* a) { delete a; }
+// merge_linear_paths(graph, &vec![]) after clear_positions: no path ends, no positions
+static void applied_merge_plan(const ac_applied* a, int with_sequences, int device, ac_merge** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!a) throw DeviceError("null pointer");
+    const ApplyResult& r = a->r;
+    const bool seqs = with_sequences && !r.seq_all.empty();
+    merge_run(r.n_total, (const ac_link*)r.links.data(), r.links.size(), r.len.data(), r.alive.data(), nullptr, 0, r.depth.data(), nullptr, nullptr, r.type.data(),
+              seqs ? r.seq_all.data() : nullptr, seqs ? r.seq_begin_all.data() : nullptr, seqs ? r.seq_all.size() : 0, nullptr, 0, device, out);
+}
+static void applied_finish(const ac_applied* a, const ac_merge* plan, int renumber, int device, ac_finished** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!a || !plan) throw DeviceError("null pointer");
+    const ApplyResult& r = a->r;
+    const bool seqs = !r.seq_all.empty();
+    finish_run(plan, r.n_total, (const ac_link*)r.links.data(), r.links.size(), r.len.data(), r.alive.data(), r.depth.data(), r.type.data(),
+               seqs ? r.seq_all.data() : nullptr, seqs ? r.seq_begin_all.data() : nullptr, seqs ? r.seq_all.size() : 0, nullptr, renumber, device, out);
+}
+int ac_applied_merge_plan(const ac_applied* a, int with_sequences, int device, ac_merge** out) {
+    return guarded([&] { applied_merge_plan(a, with_sequences, device, out); });
+}
+int ac_applied_finish(const ac_applied* a, const ac_merge* plan, int renumber, int device, ac_finished** out) {
+    return guarded([&] { applied_finish(a, plan, renumber, device, out); });
+}
+static char* malloc_string(const std::string& s, uint64_t* len) {
+    char* p = (char*)malloc(s.size() + 1);
+    if (!p) throw DeviceError("out of memory");
+    memcpy(p, s.c_str(), s.size() + 1);
+    if (len) *len = s.size();
+    return p;
+}
+int ac_applied_gfa_string(const ac_applied* a, uint32_t k, int use_other_colour, char** out, uint64_t* len) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!a) throw DeviceError("null pointer");
+        *out = malloc_string(apply_gfa_string(a->r, k, use_other_colour != 0), len);
+    });
+}
+int ac_resolve_graphs(const ac_graph* g, int device, char** bridged, char** merged, char** final_text, uint32_t* cull_count) {
+    return guarded([&] {
+        if (!bridged || !merged || !final_text || !cull_count) throw DeviceError("null pointer: out");
+        *bridged = *merged = *final_text = nullptr; *cull_count = 0;
+        if (!g) throw DeviceError("null pointer");
+        struct Free {
+            void operator()(ac_resolve* p) const { ac_resolve_free(p); }
+            void operator()(ac_applied* p) const { ac_applied_free(p); }
+            void operator()(ac_merge* p) const { ac_merge_free(p); }
+            void operator()(ac_finished* p) const { ac_finished_free(p); }
+        };
+        ac_resolve* rp = nullptr;
+        if (ac_resolve_bridges(g, device, &rp)) throw DeviceError(last_error());
+        std::unique_ptr<ac_resolve, Free> r(rp);
+        const uint32_t k = g->g.k;
+        // one pass: apply, 3_bridged's text (the first pass), merge_after_bridging = merge_linear_paths + renumber_unitigs
+        auto pass = [&](int which, std::string* bridged_text, std::unique_ptr<ac_finished, Free>* fin) {
+            ac_applied* ap = nullptr;
+            apply_on_graph(g, r.get(), which, device, &ap);
+            std::unique_ptr<ac_applied, Free> a(ap);
+            if (bridged_text) *bridged_text = apply_gfa_string(a->r, k, false);
+            ac_merge* mp = nullptr;
+            applied_merge_plan(a.get(), 1, device, &mp);
+            std::unique_ptr<ac_merge, Free> m(mp);
+            ac_finished* fp = nullptr;
+            applied_finish(a.get(), m.get(), 1, device, &fp);
+            fin->reset(fp);
+        };
+        std::string text_bridged;
+        std::unique_ptr<ac_finished, Free> fin;
+        pass(AC_APPLY_UNIQUE, &text_bridged, &fin);
+        const std::string text_merged = finish_gfa_string(fin->r, k, std::vector<FinishSeqMeta>(), false);
+        uint32_t culled = 0;
+        for (const ac_bridge& b : r->records) culled += b.culled ? 1 : 0;
+        if (culled) pass(AC_APPLY_KEPT, nullptr, &fin);      // from the unedited handle (resolve.rs:58-62)
+        const std::string text_final = finish_gfa_string(fin->r, k, std::vector<FinishSeqMeta>(), true);
+        char* b = malloc_string(text_bridged, nullptr);
+        char* m = nullptr; char* f = nullptr;
+        try { m = malloc_string(text_merged, nullptr); f = malloc_string(text_final, nullptr); }
+        catch (...) { free(b); free(m); throw; }
+        *bridged = b; *merged = m; *final_text = f; *cull_count = culled;
     });
 }
 

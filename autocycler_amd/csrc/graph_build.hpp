@@ -18,6 +18,7 @@
 #include "merge_host.hpp"
 #include "subset_host.hpp"
 #include "finish_host.hpp"
+#include "apply_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -252,6 +253,10 @@ struct FinishInput {
     const MergeResult* plan = nullptr; const int32_t* path = nullptr; uint64_t n_path = 0; bool renumber = false; uint64_t unitigs_after = 0;
 };
 void merge_finish_device(const FinishInput& in, FinishResult* out);
+// apply_bridges, reduce_depths and the two removals (resolve.rs:223-282) on the device (kernels_apply.inc): plan: apply_prepare's.  Fills the
+// per-unitig arrays over n_unitigs + the bridge unitigs, the links in get_links_for_gfa order and the bridge sequences; calls
+// components_device in the middle.  n_unitigs > 0.
+void apply_bridges_device(const ApplyInput& in, const ApplyPlan& plan, ApplyResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

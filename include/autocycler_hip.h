@@ -434,7 +434,8 @@ uint32_t ac_trim_max_unitigs(void);   /* 65536: the bit matrix of one alignment 
  * status: 0 = fine; 2 = the reference's own u32 arithmetic would overflow on this bridge (two of its paths whose weights add up to 2^32 or
  * more, or a total at or above 2^32 - 1): reported, not guessed at, and no best path.  conflicting: the flag determine_ambiguity gives with
  * all bridges present; culled / cull_rank: cull_ambiguity removed it as the cull_rank-th (1-based; 0 = kept).
- * Not done here (the caller applies the kept bridges): apply_bridges, reduce_depths, merge_linear_paths.
+ * The edit itself is further down: ac_graph_resolve_apply / ac_apply_bridges (apply_bridges, reduce_depths and the removals), then
+ * ac_applied_merge_plan and ac_applied_finish (merge_linear_paths, renumber_unitigs); ac_resolve_graphs runs all of it.
  * Errors (return 1, ac_last_error), never aborts: an entry that is 0 or beyond the weights, offsets that do not ascend, a path that enters a
  * distance job with more than ac_resolve_max_path() entries, a pair that names no path. */
 typedef struct ac_resolve ac_resolve;
@@ -537,7 +538,8 @@ void ac_components_free(ac_components*);
 /* The linear-path merge plan: what merge_linear_paths (graph_simplification.rs:315-371) would do to a graph, and the products of doing it —
  * which unitigs merge into which chains, in which order and on which strand, the new numbers, the merged sequences, depths and types
  * (merge_path :410-485, get_merge_path_depth :501-526) and the link set after the merge and delete_dangling_links.  Read-only: no handle
- * is edited; applying the plan to a graph, the positions and P lines of merged unitigs, renumber_unitigs and the GFA stay with the caller.
+ * is edited; the plan is applied by ac_merge_finish / ac_subsets_finish (renumber_unitigs, the L and P lines, the GFA) and made for a graph
+ * after resolve's apply_bridges by ac_applied_merge_plan, all further down.
  * The link entries among alive unitigs must be a SET that is closed under reverse complement: a duplicated entry, or an entry (a, b)
  * without (-b, -a), is an error (the first one by index is quoted), because the reference's sequential loop has an order-free form only
  * then.  The fixed starts and ends are the reference's own (get_fixed_unitig_starts_and_ends :190-230 on the first and last entry of every
@@ -743,6 +745,76 @@ int ac_finished_gfa_string(const ac_finished*, uint32_t k, const uint16_t* seq_i
 /* An ordinary graph handle, as ac_graph_from_gfa makes, of a finished graph made with renumber = 1 whose unitigs are all of type Other. */
 int ac_finished_to_graph(const ac_finished*, uint32_t k, const uint16_t* seq_ids, const uint32_t* seq_lengths, const char* const* filenames,
         const char* const* headers, ac_graph** out);
+
+/* apply_bridges of `autocycler resolve` with what it runs at its end (resolve.rs:223-282): the link edits, the new Bridge unitigs with their
+ * sequences, reduce_depths, delete_unitigs_not_connected_to_anchor and remove_zero_depth_unitigs — the step between ac_resolve_bridges and
+ * the merge plan.  Additions of ABI generation 13, found by name; AC_ABI_VERSION stays 13.  Read-only: the result is a new object.
+ * The reference applies the bridges one after the other; the library runs the order-free form of DESIGN.md §9k, which holds where no two
+ * applied bridges share a start or an end on either strand — what determine_ambiguity says of the bridges it leaves unflagged — and where the
+ * links among alive unitigs are a duplicate-free set closed under reverse complement.  Both are checked on the device.
+ *   bridges   in Bridge::cmp order, as ac_resolve_bridge_records gives them; apply[b] != 0 applies bridge b.  Of a record the edit reads start,
+ *             end, best_off, best_len, first_distinct, n_distinct and status.  best_paths: the pool of ac_resolve_best_paths; distinct_entries,
+ *             distinct_off (n_distinct_paths + 1), multiplicity: ac_resolve_distinct_paths.
+ *   unitigs   the result counts n_total = n_unitigs + the applied bridges with a non-empty best path: the i-th of those, in order, is unitig
+ *             n_unitigs + 1 + i, of type AC_UNITIG_BRIDGE, depth bridge_depth, its sequence the best path's members on their strands.  A bridge
+ *             with an empty best path becomes the link start -> end.  type: AC_UNITIG_ANCHOR for the anchors, AC_UNITIG_OTHER else.
+ *   depth     every visit of a unitig by a path of an applied bridge with a non-empty best path (copies counted) is one reduce_depth_by_one;
+ *             the result is the reference's f64, bit for bit (NaN stays NaN).  depth = NULL: 0.
+ *   alive     0 for what was dead at entry, for the components of the edited graph without an anchor, and then for every depth that is not
+ *             above 0.  The components are taken before the zero-depth removal, as the reference takes them.
+ *   links     the survivors and the created links whose two ends are alive, in get_links_for_gfa order over the alive originals ascending, then
+ *             the bridge unitigs: what 3_bridged.gfa prints and what ac_merge_finish wants.  The input's order matters as it does there.
+ * The number of launches (those of the components analysis apart, reported separately) follows the key widths alone, not the bridges.
+ * Errors (return 1, ac_last_error), never faults: an applied bridge with status 2; applied bridges that conflict (both are named); a start,
+ * an end or a path entry that is 0, beyond n_unitigs or dead; a start or end that is not among anchors; anchors that do not ascend; links
+ * that are no closed duplicate-free set or name no unitig; only one of seq_bytes / seq_begin; n_unitigs + bridge unitigs above 2^31 - 2; pool
+ * ranges outside their pools; a NULL out.  n_unitigs == 0 gives an empty result; without anchors everything is removed. */
+typedef struct ac_applied ac_applied;
+enum { AC_APPLY_UNIQUE = 0, AC_APPLY_KEPT = 1 };
+typedef struct {
+    uint32_t size;                  /* the library's sizeof(ac_applied_summary) */
+    uint32_t bridges_applied;
+    uint32_t direct_links;          /* of those: empty best path, a link instead of a unitig */
+    uint32_t launches;              /* the step's own: the components analysis apart */
+    uint32_t launches_components;
+    uint32_t read_backs;            /* all host round trips of the call */
+    uint64_t removed_no_anchor;     /* unitigs (bridge unitigs included) in components without an anchor */
+    uint64_t removed_zero_depth;    /* then: unitigs whose depth is not above 0 */
+    uint64_t links_in, links_out;
+    uint64_t bases_copied;          /* bytes of the bridge sequences */
+    double seconds_device;          /* the kernels of the call, by device events (the components analysis included) */
+    double seconds_copy;            /* of those, the kernel that writes the bridge sequences */
+    double seconds_components;      /* of those, the components analysis */
+} ac_applied_summary;
+int ac_apply_bridges(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive /* or NULL */,
+        const double* depth /* or NULL = 0 */, const uint32_t* anchors /* ascending unitig numbers */, uint32_t n_anchors,
+        const uint8_t* seq_bytes, const uint64_t* seq_begin /* both or neither */, const ac_bridge* bridges, uint32_t n_bridges,
+        const int32_t* best_paths, uint64_t n_best, const int32_t* distinct_entries, const uint64_t* distinct_off, const uint32_t* multiplicity,
+        uint64_t n_distinct_paths, const uint8_t* apply /* one byte per bridge */, double bridge_depth, int device, ac_applied** out);
+/* The same on a handle's links, lengths, depths and sequences with the bridges of an ac_resolve made from it.  which = AC_APPLY_UNIQUE: the
+ * bridges that do not conflict (the first pass, resolve.rs:52); AC_APPLY_KEPT: the bridges cull_ambiguity kept (the final pass, :61).
+ * bridge_depth = the handle's sequence count (:47). */
+int ac_graph_resolve_apply(const ac_graph*, const ac_resolve*, int which, int device, ac_applied** out);
+/* The arrays belong to the object.  Per unitig 1 .. n_total (any of the four may be NULL): */
+int ac_applied_unitigs(const ac_applied*, uint32_t* n_total, const uint32_t** len, const uint8_t** alive, const double** depth, const uint8_t** type);
+int ac_applied_bridge_of(const ac_applied*, const uint32_t** bridge /* unitig n_unitigs + 1 + i was made from bridge[i] */, uint32_t* n);
+int ac_applied_links(const ac_applied*, const ac_link** links, uint64_t* n);
+/* bridge unitig i = bytes[off[i] .. off[i + 1]) (off: n + 1 entries); without seq_bytes the offsets are there and *n_bytes is 0 */
+int ac_applied_bridge_sequences(const ac_applied*, const uint8_t** bytes, const uint64_t** off, uint64_t* n_bytes /* may be NULL */);
+size_t ac_applied_summary_get_sized(const ac_applied*, ac_applied_summary* out, size_t out_size);
+void ac_applied_free(ac_applied*);
+/* merge_after_bridging (resolve.rs:254-258) on the edited graph: the plan of merge_linear_paths(graph, &vec![]) after clear_positions — no
+ * path ends, no positions — and the finished graph of that plan (renumber = 1: renumber_unitigs), over the object's own arrays: the
+ * original and the bridge sequences are one array there.  Free with ac_merge_free / ac_finished_free. */
+int ac_applied_merge_plan(const ac_applied*, int with_sequences, int device, ac_merge** out);
+int ac_applied_finish(const ac_applied*, const ac_merge* plan, int renumber, int device, ac_finished** out);
+/* 3_bridged.gfa: save_gfa's text of the edited graph under its own numbers, no P lines.  *out is malloc'ed (ac_string_free). */
+int ac_applied_gfa_string(const ac_applied*, uint32_t k, int use_other_colour, char** out, uint64_t* len /* may be NULL */);
+/* resolve.rs:44-67 from a handle (a build, or ac_graph_from_gfa of 2_trimmed.gfa) to the texts of 3_bridged.gfa, 4_merged.gfa and
+ * 5_final.gfa: ac_resolve_bridges; the first pass (AC_APPLY_UNIQUE), its text, the merge and renumbering, its text; if anything was culled a
+ * second pass (AC_APPLY_KEPT) from the unedited handle, else the merged graph again; the final text with use_other_colour.  The three
+ * strings are malloc'ed (ac_string_free each). */
+int ac_resolve_graphs(const ac_graph*, int device, char** bridged, char** merged, char** final_text, uint32_t* cull_count);
 
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
@@ -1050,7 +1122,9 @@ const char* ac_version(void);
  *      ac_subsets_summary and ac_merged_paths_summary; then, still generation 13 and found by name: ac_merge_finish, ac_subsets_finish,
  *      ac_finished_unitigs, ac_finished_sequences, ac_finished_new_of_old, ac_finished_links, ac_finished_paths,
  *      ac_finished_summary_get_sized, ac_finished_free, ac_finished_gfa_string, ac_finished_to_graph with ac_finished_unitig and
- *      ac_finished_summary. */
+ *      ac_finished_summary; then, likewise: ac_apply_bridges, ac_graph_resolve_apply, ac_applied_unitigs, ac_applied_bridge_of,
+ *      ac_applied_links, ac_applied_bridge_sequences, ac_applied_summary_get_sized, ac_applied_free, ac_applied_merge_plan,
+ *      ac_applied_finish, ac_applied_gfa_string, ac_resolve_graphs with ac_applied_summary and the AC_APPLY_* values. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
