@@ -164,6 +164,14 @@ class AppliedSummary(C.Structure):      # ac_applied_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
 
 
+class CleanedSummary(C.Structure):      # ac_cleaned_summary
+    _fields_ = [(n, C.c_uint32) for n in ("size", "unitigs_in", "unitigs_out", "rounds", "rounds_per_batch", "launches", "read_backs", "reserved")] + \
+               [(n, C.c_uint64) for n in ("kept", "removed", "duplicated", "low_depth", "kept_dead_end", "absent", "links_in", "links_out")] + [("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("size", "reserved")}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -222,7 +230,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_clean_graph", "ac_graph_clean", "ac_cleaned_unitigs", "ac_cleaned_links", "ac_cleaned_summary_get_sized", "ac_cleaned_free", "ac_cleaned_merge_plan", "ac_cleaned_finish", "ac_cleaned_gfa_string", "ac_parse_tig_numbers", "ac_gfa_segment_types", "ac_clean_gfa", "ac_clean", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -391,6 +399,23 @@ def load_library(path=None):
     lib.ac_applied_merge_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_applied_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.ac_applied_gfa_string.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_clean_graph.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                   C.c_void_p, C.c_uint32, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_graph_clean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cleaned_unitigs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_double)),
+                                       C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8))]
+    lib.ac_cleaned_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Link)), C.POINTER(C.c_uint64)]
+    lib.ac_cleaned_summary_get_sized.restype = C.c_size_t
+    lib.ac_cleaned_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(CleanedSummary), C.c_size_t]
+    lib.ac_cleaned_free.argtypes = [C.c_void_p]
+    lib.ac_cleaned_free.restype = None
+    lib.ac_cleaned_merge_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cleaned_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_cleaned_gfa_string.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_parse_tig_numbers.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+    lib.ac_gfa_segment_types.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+    lib.ac_clean_gfa.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_clean.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
     lib.ac_resolve_graphs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
     lib.ac_cluster_tree_from_nodes.argtypes = [C.POINTER(ClusterNode), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ac_cluster_nodes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterNode)), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
@@ -593,6 +618,21 @@ class Graph:
         finally:
             self._lib.ac_resolve_free(r)
         return Applied(self._lib, h)
+
+    def clean(self, remove=None, duplicate=None, min_depth=None, unitig_type=None, device=0):
+        """ac_graph_clean: `autocycler clean`'s edit on this graph's links, lengths, depths and sequences.  remove / duplicate: the option's
+        string ("3, 5") or a sequence of numbers; min_depth: a float or None; unitig_type: one type per unitig (gfa_segment_types of the text the
+        graph was loaded from), None = every unitig Other.  A Cleaned."""
+        import numpy as np
+        rm, dp = _tig_numbers(self._lib, remove), _tig_numbers(self._lib, duplicate)
+        ty = None if unitig_type is None else np.ascontiguousarray(np.asarray(unitig_type, dtype=np.uint8))
+        if ty is not None and ty.shape != (self.unitig_count,):
+            raise AutocyclerError(f"unitig_type: one entry per unitig expected ({self.unitig_count}), got shape {ty.shape}")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_graph_clean(self._h, ptr(ty), ptr(rm), rm.shape[0], ptr(dp), dp.shape[0], 0 if min_depth is None else 1,
+                                                   0.0 if min_depth is None else float(min_depth), device, C.byref(h)))
+        return Cleaned(self._lib, h)
 
     def resolve_graphs(self, device=0):
         """ac_resolve_graphs: resolve.rs:44-67 on this graph -> (3_bridged.gfa, 4_merged.gfa, 5_final.gfa as bytes, cull count)"""
@@ -1447,6 +1487,154 @@ def apply_bridges(n_unitigs, links, unitig_len, anchors, bridges, apply="unique"
     _check(lib, lib.ac_apply_bridges(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(dp), ptr(an), an.shape[0], ptr(sb), ptr(sg), recs if nb else None, nb,
                                      ptr(ba), ba.shape[0], ptr(da), oa.ctypes.data, ptr(ma), ma.shape[0], ptr(fl), float(bridge_depth), device, C.byref(h)))
     return Applied(lib, h)
+
+
+class Cleaned:
+    """Owning handle of an ac_cleaned: a graph after the edits of `autocycler clean` (clean.rs:33-41), before its merge.  The arrays are copied
+    out on construction; the handle stays for merge_plan(), finish() and gfa() until close().
+    n_unitigs, n_out   the caller's n; n + 2 per duplication (copies a, b of the i-th duplicated number: n + 1 + 2 i, n + 2 + 2 i)
+    len, alive, depth, type, copy_of, reason   per unitig 1 .. n_out (reason: Cleaned.KEPT / REMOVED / DUPLICATED / LOW_DEPTH / KEPT_DEAD_END / ABSENT)
+    seq_begin      per unitig the first byte of its sequence in the caller's bytes (a copy: its original's), or None without sequences
+    links          (m, 2) int32 in get_links_for_gfa order: the originals ascending, then the copies; a multiset after a duplicated loop
+    summary        dict (unitigs_in, unitigs_out, rounds, rounds_per_batch, launches, read_backs, kept, removed, duplicated, low_depth,
+                   kept_dead_end, absent, links_in, links_out, seconds_device)"""
+    KEPT, REMOVED, DUPLICATED, LOW_DEPTH, KEPT_DEAD_END, ABSENT = range(6)
+
+    def __init__(self, lib, h):
+        self._lib, self._h = lib, h
+        nt, lp, ap, dp, tp = C.c_uint32(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint8)()
+        sp, cp, rp = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        _check(lib, lib.ac_cleaned_unitigs(h, C.byref(nt), C.byref(lp), C.byref(ap), C.byref(dp), C.byref(tp), C.byref(sp), C.byref(cp), C.byref(rp)))
+        n = self.n_out = nt.value
+        self.len, self.alive, self.depth, self.type = _take(lp, n, "<u4"), _take(ap, n, "u1"), _take(dp, n, "<f8"), _take(tp, n, "u1")
+        self.copy_of, self.reason = _take(cp, n, "<u4"), _take(rp, n, "u1")
+        self.seq_begin = _take(sp, n, "<u8") if sp else None
+        kp, kn = C.POINTER(Link)(), C.c_uint64()
+        _check(lib, lib.ac_cleaned_links(h, C.byref(kp), C.byref(kn)))
+        self.links = _take(kp, 2 * kn.value, "<i4").reshape(-1, 2)
+        sm = CleanedSummary()
+        assert lib.ac_cleaned_summary_get_sized(h, C.byref(sm), C.sizeof(CleanedSummary)) == C.sizeof(CleanedSummary) == sm.size
+        self.summary = sm.as_dict()
+        self.n_unitigs = sm.unitigs_in
+
+    def close(self):
+        if self._h:
+            self._lib.ac_cleaned_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def merge_plan(self, with_sequences=True, device=0):
+        """ac_cleaned_merge_plan: merge_linear_paths(graph, &vec![]); the plan's handle stays open for finish().  Refused after a duplicated loop."""
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_cleaned_merge_plan(self._h, int(bool(with_sequences)), device, C.byref(h)))
+        return MergePlan(self._lib, h, self.n_out, keep=True)
+
+    def finish(self, plan, renumber=True, device=0):
+        """ac_cleaned_finish: the graph after that merge (renumber: renumber_unitigs), a Finished"""
+        if getattr(plan, "_h", None) is None:
+            raise AutocyclerError("Cleaned.finish: the plan's handle must be open (Cleaned.merge_plan)")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_cleaned_finish(self._h, plan._h, 1 if renumber else 0, device, C.byref(h)))
+        return Finished(self._lib, h)
+
+    def gfa(self, k, use_other_colour=True):
+        """ac_cleaned_gfa_string: the edited graph under its own numbers, before the merge (bytes); no P lines"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.ac_cleaned_gfa_string(self._h, k, 1 if use_other_colour else 0, C.byref(out), C.byref(n)))
+        text = C.string_at(out.value, n.value)
+        self._lib.ac_string_free(out)
+        return text
+
+
+def parse_tig_numbers(text, lib_path=None):
+    """ac_parse_tig_numbers: parse_tig_numbers of clean.rs — "4, 5,6" -> [4, 5, 6]; None -> []; a piece that is no u32 raises"""
+    lib = load_library(lib_path)
+    out, n = C.c_void_p(), C.c_uint32()
+    _check(lib, lib.ac_parse_tig_numbers(None if text is None else text.encode(), C.byref(out), C.byref(n)))
+    v = list((C.c_uint32 * n.value).from_address(out.value)) if n.value else []
+    lib.ac_string_free(out)
+    return v
+
+
+def _tig_numbers(lib, numbers):
+    """an option of clean as the ABI takes it: its string parsed by the library, or a sequence of numbers sorted as parse_tig_numbers sorts"""
+    import numpy as np
+    if numbers is None:
+        return np.zeros(0, dtype=np.uint32)
+    if isinstance(numbers, (str, bytes)):
+        out, n = C.c_void_p(), C.c_uint32()
+        _check(lib, lib.ac_parse_tig_numbers(numbers.encode() if isinstance(numbers, str) else numbers, C.byref(out), C.byref(n)))
+        v = list((C.c_uint32 * n.value).from_address(out.value)) if n.value else []
+        lib.ac_string_free(out)
+        return np.asarray(v, dtype=np.uint32)
+    return np.sort(np.ascontiguousarray(np.asarray(list(numbers), dtype=np.uint32).reshape(-1)))
+
+
+def gfa_segment_types(gfa_text, lib_path=None):
+    """ac_gfa_segment_types: the type of every S line of a GFA text from its CL:Z colour (MergePlan.OTHER / ANCHOR / CONSENTIG / BRIDGE), a uint8 array"""
+    import numpy as np
+    lib = load_library(lib_path)
+    b = gfa_text.encode() if isinstance(gfa_text, str) else gfa_text
+    out, n = C.c_void_p(), C.c_uint32()
+    _check(lib, lib.ac_gfa_segment_types(b, len(b), C.byref(out), C.byref(n)))
+    v = np.frombuffer(C.string_at(out.value, n.value), dtype=np.uint8).copy()
+    lib.ac_string_free(out)
+    return v
+
+
+def clean_graph(n_unitigs, links, unitig_len, depth=None, unitig_type=None, alive=None, sequences=None, remove=None, duplicate=None, min_depth=None, device=0,
+                lib_path=None):
+    """ac_clean_graph: the edits of `autocycler clean` on plain arrays.  links: (a, b) pairs of signed unitig numbers in L-line order, a set closed
+    under reverse complement; remove / duplicate: the option's string or a sequence of numbers; min_depth: a float or None; sequences: one bytes
+    object per unitig, or (uint8 array, uint64 first bytes).  A Cleaned."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+
+    def per_unitig(values, dtype, what):
+        if values is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+        if a.shape != (n_unitigs,):
+            raise AutocyclerError(f"{what}: one entry per unitig expected ({n_unitigs}), got shape {a.shape}")
+        return a
+    ln, dp, ty = per_unitig(unitig_len, np.uint32, "unitig_len"), per_unitig(depth, np.float64, "depth"), per_unitig(unitig_type, np.uint8, "unitig_type")
+    al = _bytes_per_unitig(alive, n_unitigs, "alive")
+    sb = sg = None
+    if isinstance(sequences, tuple):
+        sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), per_unitig(sequences[1], np.uint64, "sequences[1]")
+    elif sequences is not None:
+        if len(sequences) != n_unitigs:
+            raise AutocyclerError(f"sequences: one entry per unitig expected ({n_unitigs}), got {len(sequences)}")
+        sg = np.zeros(max(n_unitigs, 1), dtype=np.uint64)
+        sg[1:n_unitigs] = np.cumsum([len(x) for x in sequences[:-1]], dtype=np.uint64) if n_unitigs > 1 else []
+        sb = np.frombuffer(b"".join(bytes(x) for x in sequences) + b"\0", dtype=np.uint8)
+    rm, du = _tig_numbers(lib, remove), _tig_numbers(lib, duplicate)
+    if ln is not None and ln.size == 0:
+        ln = np.zeros(1, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_clean_graph(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(dp), ptr(ty), ptr(al), ptr(sb), ptr(sg), ptr(rm), rm.shape[0], ptr(du), du.shape[0],
+                                   0 if min_depth is None else 1, 0.0 if min_depth is None else float(min_depth), device, C.byref(h)))
+    return Cleaned(lib, h)
+
+
+def clean_gfa(text, remove=None, duplicate=None, min_depth=None, device=0, lib_path=None):
+    """ac_clean_gfa: `autocycler clean` from a GFA text to the cleaned GFA text (bytes).  remove / duplicate: the option's string, or None."""
+    lib = load_library(lib_path)
+    b = text.encode() if isinstance(text, str) else text
+    out, n = C.c_void_p(), C.c_uint64()
+    enc = lambda v: None if v is None else (v.encode() if isinstance(v, str) else ",".join(str(int(x)) for x in v).encode())
+    _check(lib, lib.ac_clean_gfa(b, len(b), enc(remove), enc(duplicate), 0 if min_depth is None else 1, 0.0 if min_depth is None else float(min_depth), device,
+                                 C.byref(out), C.byref(n)))
+    res = C.string_at(out.value, n.value)
+    lib.ac_string_free(out)
+    return res
 
 
 def graph_subsets(graph, cluster_of_seq, n_clusters=None, device=0, lib_path=None):

@@ -1,8 +1,9 @@
 // C ABI, the neighbouring steps on a graph handle or on the caller's arrays: end repair, pairwise distances, trim, resolve, cluster, read depths, the
-// verifier, decompress, the GFA reload, and the self-tests of the device primitives.
+// verifier, decompress, the GFA reload, `clean` (with its file command, a thin wrapper around the text entry), and the self-tests of the device primitives.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <fstream>
 #include <memory>
 #include <string>
 
@@ -963,6 +964,206 @@ int ac_resolve_graphs(const ac_graph* g, int device, char** bridged, char** merg
         try { m = malloc_string(text_merged, nullptr); f = malloc_string(text_final, nullptr); }
         catch (...) { free(b); free(m); throw; }
         *bridged = b; *merged = m; *final_text = f; *cull_count = culled;
+    });
+}
+
+// ---- `autocycler clean`, the edit: remove_unitigs_by_number, duplicate_unitig_by_number and remove_low_depth_unitigs on the device
+// (kernels_clean.inc); the number lists, the sequential duplication over the gathered entries and the text on the host (clean_host.cpp).  The
+// composed entries hand the edited arrays to the merge plan and the finished graph above; ac_clean_gfa is clean.rs:27-43 from text to text ----
+struct ac_cleaned {
+    CleanResult r;
+    ac_cleaned_summary summary;
+};
+static_assert((int)AC_CLEAN_KEPT == (int)CLEAN_KEPT && (int)AC_CLEAN_REMOVED == (int)CLEAN_REMOVED && (int)AC_CLEAN_DUPLICATED == (int)CLEAN_DUPLICATED &&
+              (int)AC_CLEAN_LOW_DEPTH == (int)CLEAN_LOW_DEPTH && (int)AC_CLEAN_KEPT_DEAD_END == (int)CLEAN_KEPT_DEAD_END && (int)AC_CLEAN_ABSENT == (int)CLEAN_ABSENT,
+              "the AC_CLEAN_* values are clean_host.hpp's");
+static void clean_run(const CleanInput& in, int device, ac_cleaned** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    clean_prepare(in);
+    auto h = std::make_unique<ac_cleaned>();
+    if (in.n_unitigs == 0) {      // (nothing to launch: no device is asked for)
+        if (in.n_links) throw DeviceError(components_bad_link_message(0, in.links[0].a, in.links[0].b, 0));
+        clean_empty(&h->r);
+    } else {
+        DeviceCall call(device);
+        clean_device(in, &h->r);
+    }
+    clean_finish(in, &h->r);
+    const CleanResult& r = h->r;
+    ac_cleaned_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.unitigs_in = r.n_unitigs; sm.unitigs_out = r.n_out; sm.rounds = r.rounds; sm.rounds_per_batch = CLEAN_ROUNDS_PER_BATCH;
+    sm.launches = r.stats.launches; sm.read_backs = r.stats.read_backs; sm.kept = r.count[CLEAN_KEPT]; sm.removed = r.count[CLEAN_REMOVED];
+    sm.duplicated = r.count[CLEAN_DUPLICATED]; sm.low_depth = r.count[CLEAN_LOW_DEPTH]; sm.kept_dead_end = r.count[CLEAN_KEPT_DEAD_END]; sm.absent = r.count[CLEAN_ABSENT];
+    sm.links_in = r.links_in; sm.links_out = r.links.size(); sm.seconds_device = r.stats.seconds_device;
+    *out = h.release();
+}
+int ac_clean_graph(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const double* depth, const uint8_t* type, const uint8_t* alive,
+                   const uint8_t* seq_bytes, const uint64_t* seq_begin, const uint32_t* remove, uint32_t n_remove, const uint32_t* duplicate, uint32_t n_duplicate,
+                   int has_min_depth, double min_depth, int device, ac_cleaned** out) {
+    return guarded([&] {
+        CleanInput in;
+        in.n_unitigs = n_unitigs; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.depth = depth; in.type = type; in.alive = alive;
+        in.seq_bytes = seq_bytes; in.seq_begin = seq_begin;
+        if (seq_bytes && seq_begin && unitig_len)
+            for (uint32_t u = 0; u < n_unitigs; u++) in.seq_total = std::max<uint64_t>(in.seq_total, seq_begin[u] + unitig_len[u]);
+        in.remove = remove; in.n_remove = n_remove; in.duplicate = duplicate; in.n_duplicate = n_duplicate; in.has_min_depth = has_min_depth != 0; in.min_depth = min_depth;
+        clean_run(in, device, out);
+    });
+}
+static void clean_on_graph(const ac_graph* g, const uint8_t* type, const uint32_t* remove, uint32_t n_remove, const uint32_t* duplicate, uint32_t n_duplicate, int has_min_depth,
+                           double min_depth, const std::string& name, int device, ac_cleaned** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!g) throw DeviceError("null pointer");
+    if (!g->host_arrays) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+    const FinalGraph& f = g->g;
+    const bool seqs = f.seq_block.p && f.seq_begin;
+    CleanInput in;
+    in.n_unitigs = f.n_unitigs; in.links = f.links; in.n_links = f.n_links; in.unitig_len = f.seq_len; in.depth = f.depth; in.type = type;
+    in.seq_bytes = seqs ? (const uint8_t*)f.seq_block.p : nullptr; in.seq_begin = seqs ? f.seq_begin : nullptr; in.seq_total = seqs ? f.seq_block.bytes : 0;
+    in.remove = remove; in.n_remove = n_remove; in.duplicate = duplicate; in.n_duplicate = n_duplicate; in.has_min_depth = has_min_depth != 0; in.min_depth = min_depth;
+    in.name = name;
+    clean_run(in, device, out);
+}
+int ac_graph_clean(const ac_graph* g, const uint8_t* type, const uint32_t* remove, uint32_t n_remove, const uint32_t* duplicate, uint32_t n_duplicate, int has_min_depth,
+                   double min_depth, int device, ac_cleaned** out) {
+    return guarded([&] { clean_on_graph(g, type, remove, n_remove, duplicate, n_duplicate, has_min_depth, min_depth, "the graph", device, out); });
+}
+int ac_cleaned_unitigs(const ac_cleaned* c, uint32_t* n_out, const uint32_t** len, const uint8_t** alive, const double** depth, const uint8_t** type,
+                       const uint64_t** seq_begin, const uint32_t** copy_of, const uint8_t** reason) {
+    return guarded([&] {
+        if (!c || !n_out) throw DeviceError("null pointer");
+        *n_out = c->r.n_out;
+        if (len) *len = c->r.len.data();
+        if (alive) *alive = c->r.alive.data();
+        if (depth) *depth = c->r.depth.data();
+        if (type) *type = c->r.type.data();
+        if (seq_begin) *seq_begin = c->r.seq_begin.empty() ? nullptr : c->r.seq_begin.data();
+        if (copy_of) *copy_of = c->r.copy_of.data();
+        if (reason) *reason = c->r.reason.data();
+    });
+}
+int ac_cleaned_links(const ac_cleaned* c, const ac_link** links, uint64_t* n) {
+    return guarded([&] {
+        if (!c || !links || !n) throw DeviceError("null pointer");
+        *links = (const ac_link*)c->r.links.data(); *n = c->r.links.size();
+    });
+}
+size_t ac_cleaned_summary_get_sized(const ac_cleaned* c, ac_cleaned_summary* out, size_t out_size) {
+    if (c && out) memcpy(out, &c->summary, std::min(out_size, sizeof(ac_cleaned_summary)));
+    return sizeof(ac_cleaned_summary);
+}
+void ac_cleaned_free(ac_cleaned* c) { delete c; }
+// merge_linear_paths(graph, &vec![]) (clean.rs:114): no path ends, no positions.  A duplicated loop left a link multiset: the plan's own
+// check refuses it.
+static void cleaned_merge_plan(const ac_cleaned* c, int with_sequences, int device, ac_merge** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!c) throw DeviceError("null pointer");
+    const CleanResult& r = c->r;
+    const bool seqs = with_sequences && !r.seq_all.empty();
+    merge_run(r.n_out, (const ac_link*)r.links.data(), r.links.size(), r.len.data(), r.alive.data(), nullptr, 0, r.depth.data(), nullptr, nullptr, r.type.data(),
+              seqs ? r.seq_all.data() : nullptr, seqs ? r.seq_begin.data() : nullptr, seqs ? r.seq_all.size() : 0, nullptr, 0, device, out);
+}
+static void cleaned_finish(const ac_cleaned* c, const ac_merge* plan, int renumber, int device, ac_finished** out) {
+    if (!out) throw DeviceError("null pointer: out");
+    *out = nullptr;
+    if (!c || !plan) throw DeviceError("null pointer");
+    const CleanResult& r = c->r;
+    const bool seqs = !r.seq_all.empty();
+    finish_run(plan, r.n_out, (const ac_link*)r.links.data(), r.links.size(), r.len.data(), r.alive.data(), r.depth.data(), r.type.data(),
+               seqs ? r.seq_all.data() : nullptr, seqs ? r.seq_begin.data() : nullptr, seqs ? r.seq_all.size() : 0, nullptr, renumber, device, out);
+}
+int ac_cleaned_merge_plan(const ac_cleaned* c, int with_sequences, int device, ac_merge** out) {
+    return guarded([&] { cleaned_merge_plan(c, with_sequences, device, out); });
+}
+int ac_cleaned_finish(const ac_cleaned* c, const ac_merge* plan, int renumber, int device, ac_finished** out) {
+    return guarded([&] { cleaned_finish(c, plan, renumber, device, out); });
+}
+int ac_cleaned_gfa_string(const ac_cleaned* c, uint32_t k, int use_other_colour, char** out, uint64_t* len) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!c) throw DeviceError("null pointer");
+        *out = malloc_string(clean_gfa_string(c->r, k, use_other_colour != 0), len);
+    });
+}
+int ac_parse_tig_numbers(const char* text, uint32_t** numbers, uint32_t* n) {
+    return guarded([&] {
+        if (!numbers || !n) throw DeviceError("null pointer: out");
+        *numbers = nullptr; *n = 0;
+        const std::vector<uint32_t> v = clean_parse_tig_numbers(text);
+        uint32_t* p = (uint32_t*)malloc((v.size() + 1) * sizeof(uint32_t));
+        if (!p) throw DeviceError("out of memory");
+        if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(uint32_t));
+        *numbers = p; *n = (uint32_t)v.size();
+    });
+}
+int ac_gfa_segment_types(const char* gfa_text, uint64_t len, uint8_t** types, uint32_t* n) {
+    return guarded([&] {
+        if (!types || !n) throw DeviceError("null pointer: out");
+        *types = nullptr; *n = 0;
+        if (!gfa_text && len) throw DeviceError("null pointer: gfa_text");
+        const std::vector<uint8_t> v = clean_gfa_types(gfa_text, len);
+        uint8_t* p = (uint8_t*)malloc(v.size() + 1);
+        if (!p) throw DeviceError("out of memory");
+        if (!v.empty()) memcpy(p, v.data(), v.size());
+        *types = p; *n = (uint32_t)v.size();
+    });
+}
+static std::string clean_gfa_text(const char* gfa_text, uint64_t len, const std::string& name, const char* remove, const char* duplicate, int has_min_depth,
+                                  double min_depth, int device) {
+    {
+        if (!gfa_text && len) throw DeviceError("null pointer: gfa_text");
+        struct Free {
+            void operator()(ac_cleaned* p) const { ac_cleaned_free(p); }
+            void operator()(ac_merge* p) const { ac_merge_free(p); }
+            void operator()(ac_finished* p) const { ac_finished_free(p); }
+        };
+        // clean.rs:27-32: both lists are parsed before the graph is loaded, and checked against it before anything is edited
+        const std::vector<uint32_t> rm = clean_parse_tig_numbers(remove), dup = clean_parse_tig_numbers(duplicate);
+        ac_graph g;
+        std::vector<SeqMeta> meta;
+        load_gfa(gfa_text, len, &g.g, &meta);
+        const std::vector<uint8_t> types = clean_gfa_types(gfa_text, len);
+        if (types.size() != g.g.n_unitigs) throw DeviceError("clean: the S lines of the text and the loaded graph disagree (internal error)");
+        ac_cleaned* cp = nullptr;
+        clean_on_graph(&g, types.data(), rm.data(), (uint32_t)rm.size(), dup.data(), (uint32_t)dup.size(), has_min_depth, min_depth, name, device, &cp);
+        std::unique_ptr<ac_cleaned, Free> c(cp);
+        ac_merge* mp = nullptr;
+        cleaned_merge_plan(c.get(), 1, device, &mp);
+        std::unique_ptr<ac_merge, Free> m(mp);
+        ac_finished* fp = nullptr;
+        cleaned_finish(c.get(), m.get(), 1, device, &fp);
+        std::unique_ptr<ac_finished, Free> f(fp);
+        return finish_gfa_string(f->r, g.g.k, std::vector<FinishSeqMeta>(), true);      // save_gfa(out, &vec![], true)
+    }
+}
+int ac_clean_gfa(const char* gfa_text, uint64_t len, const char* remove, const char* duplicate, int has_min_depth, double min_depth, int device, char** out_text,
+                 uint64_t* out_len) {
+    return guarded([&] {
+        if (!out_text) throw DeviceError("null pointer: out");
+        *out_text = nullptr;
+        *out_text = malloc_string(clean_gfa_text(gfa_text, len, "the graph", remove, duplicate, has_min_depth, min_depth, device), out_len);
+    });
+}
+// The whole command (clean.rs:23-45): check_if_file_exists, then the above from in_gfa to out_gfa.
+int ac_clean(const char* in_gfa, const char* out_gfa, const char* remove, const char* duplicate, int has_min_depth, double min_depth, int device) {
+    return guarded([&] {
+        if (!in_gfa || !out_gfa) throw DeviceError("null pointer: in_gfa and out_gfa are required");
+        std::string text;
+        {
+            std::ifstream f(in_gfa, std::ios::binary);
+            if (!f) throw DeviceError(std::string("file does not exist: ") + in_gfa);
+            text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        }
+        const std::string out = clean_gfa_text(text.data(), text.size(), in_gfa, remove, duplicate, has_min_depth, min_depth, device);
+        std::ofstream o(out_gfa, std::ios::binary);
+        o.write(out.data(), (std::streamsize)out.size());
+        o.close();
+        if (!o) throw DeviceError(std::string("failed to write ") + out_gfa);
     });
 }
 

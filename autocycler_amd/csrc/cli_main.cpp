@@ -2,6 +2,7 @@
 //   -i/--assemblies_dir DIR  -a/--autocycler_dir DIR  [--kmer 51] [--max_contigs 25] [-t/--threads 8] [--device 0 | --devices 0,1,..] [--stats]
 // (--devices: one job over several GPUs of the node through ac_compress_build_multi; --stats: the graph's connected components and
 // topology after the usual lines, ac_graph_components; neither is a flag of the reference)
+// Two more commands sit next to it: `decompress` and `clean` (below).
 // Writes DIR/input_assemblies.gfa and DIR/input_assemblies.yaml (compress.rs:45-46) through the C ABI
 // (ac_compress_dir: C++ loader + end repair, HIP graph build, host tail, buffered GFA writer).
 #include <chrono>
@@ -42,8 +43,45 @@ static int decompress_main(int argc, char** argv) {
     return 0;
 }
 
+// `autocycler clean` (main.rs: Clean): -i/--in_gfa FILE  -o/--out_gfa FILE  [-r/--remove 1,2]  [-d/--duplicate 3]  [-m/--min_depth 1.5]  [--device 0]
+static int clean_main(int argc, char** argv) {
+    std::string in, out, remove, duplicate, depth;
+    bool has_remove = false, has_duplicate = false, has_depth = false;
+    int device = 0;
+    const char* use = "Usage: autocycler-compress clean --in_gfa <GFA> --out_gfa <GFA> [--remove <TIGS>] [--duplicate <TIGS>] [--min_depth <DEPTH>] [--device 0]\n";
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto val = [&]() -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", a.c_str()); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-i" || a == "--in_gfa") in = val();
+        else if (a == "-o" || a == "--out_gfa") out = val();
+        else if (a == "-r" || a == "--remove") { remove = val(); has_remove = true; }
+        else if (a == "-d" || a == "--duplicate") { duplicate = val(); has_duplicate = true; }
+        else if (a == "-m" || a == "--min_depth") { depth = val(); has_depth = true; }
+        else if (a == "--device") device = atoi(val());
+        else { fprintf(stderr, "error: unexpected argument '%s'\n%s", a.c_str(), use); return 2; }
+    }
+    if (in.empty() || out.empty()) { fprintf(stderr, "%s", use); return 2; }
+    double min_depth = 0;
+    if (has_depth) {
+        char* end = nullptr;
+        min_depth = strtod(depth.c_str(), &end);
+        if (depth.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '--min_depth <MIN_DEPTH>'\n", depth.c_str()); return 2; }
+    }
+    fprintf(stderr, "\nStarting autocycler clean\nSettings:\n  --in_gfa %s\n  --out_gfa %s\n", in.c_str(), out.c_str());
+    if (ac_clean(in.c_str(), out.c_str(), has_remove ? remove.c_str() : nullptr, has_duplicate ? duplicate.c_str() : nullptr, has_depth ? 1 : 0, min_depth, device) != 0) {
+        fprintf(stderr, "\nError: %s\n", ac_last_error());
+        return 1;
+    }
+    fprintf(stderr, "\nFinished!\nCleaned graph: %s\n\n", out.c_str());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "decompress") == 0) return decompress_main(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "clean") == 0) return clean_main(argc, argv);
     std::string in, out;
     unsigned k = 51, max_contigs = 25;
     int threads = 8, device = 0;

@@ -19,6 +19,7 @@
 #include "subset_host.hpp"
 #include "finish_host.hpp"
 #include "apply_host.hpp"
+#include "clean_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -257,6 +258,10 @@ void merge_finish_device(const FinishInput& in, FinishResult* out);
 // per-unitig arrays over n_unitigs + the bridge unitigs, the links in get_links_for_gfa order and the bridge sequences; calls
 // components_device in the middle.  n_unitigs > 0.
 void apply_bridges_device(const ApplyInput& in, const ApplyPlan& plan, ApplyResult* out);
+// `autocycler clean`'s edit (clean.rs:33-41) on the device (kernels_clean.inc): removal, duplication (clean_duplicate_edit on the host over the
+// entries the device gathers) and remove_low_depth_unitigs in rounds.  in: checked by clean_prepare.  Fills the per-unitig arrays over
+// n_unitigs + 2 per duplication, the links in get_links_for_gfa order, the rounds and the stats.  n_unitigs > 0.
+void clean_device(const CleanInput& in, CleanResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

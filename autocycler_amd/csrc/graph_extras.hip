@@ -2,7 +2,8 @@
 // and device decompress (kernels_verify.inc); trim's path-overlap alignment (kernels_trim.inc); resolve's path distances (kernels_resolve.inc);
 // cluster's UPGMA merge loop (kernels_cluster.inc) and the QC of its clusters (kernels_cluster_qc.inc); connected components and topology
 // (kernels_components.inc); the linear-path merge plan (kernels_merge.inc); sequence subsets and the paths over merged unitigs (kernels_subset.inc);
-// the finished graph after a merge: order, renumbering, L lines (kernels_finish.inc); resolve's apply_bridges with its removals (kernels_apply.inc).
+// the finished graph after a merge: order, renumbering, L lines (kernels_finish.inc); resolve's apply_bridges with its removals (kernels_apply.inc);
+// clean's removal, duplication and low-depth rounds (kernels_clean.inc).
 #include "graph_impl.hpp"
 
 namespace ac {
@@ -18,5 +19,6 @@ namespace ac {
 #include "kernels_subset.inc"  // ac_graph_subsets / ac_subsets_from_paths / ac_subsets_merged_paths: what each cluster of sequences keeps (f-11)
 #include "kernels_finish.inc"  // ac_merge_finish / ac_subsets_finish: the S-line order, renumber_unitigs, the L and P lines after a merge (f-12)
 #include "kernels_apply.inc"   // ac_apply_bridges / ac_graph_resolve_apply: apply_bridges, reduce_depths and the two removals of `autocycler resolve` (f-13)
+#include "kernels_clean.inc"   // ac_clean_graph / ac_graph_clean: remove, duplicate and remove_low_depth_unitigs of `autocycler clean` (f-14)
 
 }  // namespace ac

@@ -816,6 +816,81 @@ int ac_applied_gfa_string(const ac_applied*, uint32_t k, int use_other_colour, c
  * strings are malloc'ed (ac_string_free each). */
 int ac_resolve_graphs(const ac_graph*, int device, char** bridged, char** merged, char** final_text, uint32_t* cull_count);
 
+/* `autocycler clean` (clean.rs:23-45): the command that edits a consensus graph which is not fully resolved — the user's tigs out
+ * (remove_unitigs_by_number), a tig that two replicons share doubled (duplicate_unitig_by_number), low-depth tigs out where that leaves no
+ * dead end (remove_low_depth_unitigs; unitig_graph.rs:588-721), then merge_linear_paths, renumber_unitigs and save_gfa.  Additions of ABI
+ * generation 13, found by name; AC_ABI_VERSION stays 13.  Read-only: the result is a new object.
+ *   links      one entry per L line in L-line order (unitigs ascending, a unitig's forward links before its reverse links: ac_links, or a loaded
+ *              GFA); among alive unitigs a duplicate-free set closed under reverse complement.  Anything else is an error that quotes the
+ *              first offending entry.  The order inside a list decides which link of a duplicated tig goes to which copy.
+ *   remove, duplicate   ascending unitig numbers (ac_parse_tig_numbers); every number must name a unitig alive at entry, or the error is
+ *              "<graph> does not contain tig N".  A number listed twice in remove is harmless.
+ *   duplicate  one number at a time, ascending, against the graph as it is then: the tig must have exactly two non-self links, counted over its
+ *              forward then its reverse list ("unitig N does not contain exactly two non-self links"); copies a and b of duplicate[i] are
+ *              unitigs n_unitigs + 1 + 2 i and n_unitigs + 2 + 2 i, same bytes and type, half the depth; the first non-self link goes to a, the
+ *              second to b, self links to both.  A number that was removed, or duplicated earlier in the call, is an error (the reference
+ *              panics there).  A loop u+ -> u+ is re-created once from each strand's list, so each copy carries it TWICE, as in the reference;
+ *              a hairpin once.  ac_cleaned_links reports that multiset literally; the composed entries below refuse it with the merge plan's
+ *              duplicate-entry error, whose order-free form holds for sets only.
+ *   min_depth  with has_min_depth != 0: the unitigs are walked from the last (the copies, b before a) to the first; one whose depth is not
+ *              above min_depth (a NaN on either side counts as low) goes iff every neighbour it leads to or comes from keeps another entry on
+ *              that side; each decision sees the deletions before it.  The device runs the round form of DESIGN.md 9l: the same result, the
+ *              number of rounds in the summary; a chain of n low unitigs takes n rounds.
+ *   result     over n_out = n_unitigs + 2 * n_duplicate unitigs: alive, depth, type, length, seq_begin (a copy points at its original's bytes;
+ *              NULL without sequences), copy_of (0 for the originals) and a reason code; the links among alive unitigs in get_links_for_gfa
+ *              order over the originals ascending, then the copies: what ac_merge_finish wants.
+ * The number of launches is a constant plus a constant per batch of rounds_per_batch rounds; the host reads one counter per batch.
+ * Errors (return 1, ac_last_error), never faults; n_unitigs == 0 gives an empty result. */
+typedef struct ac_cleaned ac_cleaned;
+enum { AC_CLEAN_KEPT = 0, AC_CLEAN_REMOVED = 1, AC_CLEAN_DUPLICATED = 2, AC_CLEAN_LOW_DEPTH = 3,
+       AC_CLEAN_KEPT_DEAD_END = 4 /* low, but kept to avoid a dead end */, AC_CLEAN_ABSENT = 5 /* not alive at entry */ };
+typedef struct {
+    uint32_t size;                  /* the library's sizeof(ac_cleaned_summary) */
+    uint32_t unitigs_in, unitigs_out;   /* n_unitigs; n_unitigs + 2 per duplication */
+    uint32_t rounds;                /* of the low-depth step */
+    uint32_t rounds_per_batch;      /* rounds between two read-backs */
+    uint32_t launches, read_backs;
+    uint32_t reserved;
+    uint64_t kept, removed, duplicated, low_depth, kept_dead_end, absent;   /* unitigs per reason code */
+    uint64_t links_in, links_out;
+    double seconds_device;          /* the kernels of the call, by device events */
+} ac_cleaned_summary;
+int ac_clean_graph(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const double* depth /* or NULL = 0 */,
+        const uint8_t* type /* AC_UNITIG_*, or NULL = Other */, const uint8_t* alive /* or NULL */, const uint8_t* seq_bytes,
+        const uint64_t* seq_begin /* both or neither */, const uint32_t* remove, uint32_t n_remove, const uint32_t* duplicate, uint32_t n_duplicate,
+        int has_min_depth, double min_depth, int device, ac_cleaned** out);
+/* The same on a handle's links, lengths, depths and sequences.  A handle holds no types: type = one AC_UNITIG_* byte per unitig
+ * (ac_gfa_segment_types of the text the handle was loaded from), or NULL = every unitig Other. */
+int ac_graph_clean(const ac_graph*, const uint8_t* type, const uint32_t* remove, uint32_t n_remove, const uint32_t* duplicate, uint32_t n_duplicate,
+        int has_min_depth, double min_depth, int device, ac_cleaned** out);
+/* The arrays belong to the object.  Per unitig 1 .. n_out (any of the seven may be NULL): */
+int ac_cleaned_unitigs(const ac_cleaned*, uint32_t* n_out, const uint32_t** len, const uint8_t** alive, const double** depth, const uint8_t** type,
+        const uint64_t** seq_begin, const uint32_t** copy_of, const uint8_t** reason);
+int ac_cleaned_links(const ac_cleaned*, const ac_link** links, uint64_t* n);
+size_t ac_cleaned_summary_get_sized(const ac_cleaned*, ac_cleaned_summary* out, size_t out_size);
+void ac_cleaned_free(ac_cleaned*);
+/* merge_graph (clean.rs:111-117) on the edited graph: the plan of merge_linear_paths(graph, &vec![]) — no path ends, no positions — and the
+ * finished graph of that plan (renumber = 1: renumber_unitigs), over the object's own arrays.  Free with ac_merge_free / ac_finished_free.
+ * After a duplicated loop the links are a multiset and both entries fail with the merge plan's duplicate-entry error. */
+int ac_cleaned_merge_plan(const ac_cleaned*, int with_sequences, int device, ac_merge** out);
+int ac_cleaned_finish(const ac_cleaned*, const ac_merge* plan, int renumber, int device, ac_finished** out);
+/* save_gfa's text of the edited graph under its own numbers, before the merge; no P lines.  *out is malloc'ed (ac_string_free). */
+int ac_cleaned_gfa_string(const ac_cleaned*, uint32_t k, int use_other_colour, char** out, uint64_t* len /* may be NULL */);
+/* parse_tig_numbers (clean.rs:142-149): spaces removed, split at ',', every piece a u32, sorted.  text == NULL: the option is absent, an empty
+ * list.  A piece that does not parse (the empty string is one) fails with "failed to parse '<piece>' as a node number".  *numbers is
+ * malloc'ed (free it with ac_string_free). */
+int ac_parse_tig_numbers(const char* text, uint32_t** numbers, uint32_t* n);
+/* The type of every S line of a GFA text, in file order, from its CL:Z colour as Unitig::from_segment_line reads it (unitig.rs:79-87):
+ * AC_UNITIG_* bytes.  ac_graph_from_gfa drops the colours; this entry is how a caller keeps them.  *types is malloc'ed (ac_string_free). */
+int ac_gfa_segment_types(const char* gfa_text, uint64_t len, uint8_t** types, uint32_t* n);
+/* clean.rs:27-43 from text to text: parse both lists, load the graph (segments numbered 1, 2, 3, ... as ac_graph_from_gfa wants them), check
+ * the numbers, remove, duplicate, low depth, merge, renumber, and save_gfa(out, &vec![], true): no P lines, use_other_colour, KM:i of the
+ * input (0 without one).  remove / duplicate: the option's string, or NULL.  *out_text is malloc'ed (ac_string_free). */
+int ac_clean_gfa(const char* gfa_text, uint64_t len, const char* remove, const char* duplicate, int has_min_depth, double min_depth, int device,
+        char** out_text, uint64_t* out_len /* may be NULL */);
+/* The whole command: in_gfa must exist; the cleaned graph is written to out_gfa.  "<in_gfa> does not contain tig N" names the file. */
+int ac_clean(const char* in_gfa, const char* out_gfa, const char* remove, const char* duplicate, int has_min_depth, double min_depth, int device);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -1124,7 +1199,10 @@ const char* ac_version(void);
  *      ac_finished_summary_get_sized, ac_finished_free, ac_finished_gfa_string, ac_finished_to_graph with ac_finished_unitig and
  *      ac_finished_summary; then, likewise: ac_apply_bridges, ac_graph_resolve_apply, ac_applied_unitigs, ac_applied_bridge_of,
  *      ac_applied_links, ac_applied_bridge_sequences, ac_applied_summary_get_sized, ac_applied_free, ac_applied_merge_plan,
- *      ac_applied_finish, ac_applied_gfa_string, ac_resolve_graphs with ac_applied_summary and the AC_APPLY_* values. */
+ *      ac_applied_finish, ac_applied_gfa_string, ac_resolve_graphs with ac_applied_summary and the AC_APPLY_* values; then, likewise:
+ *      ac_clean_graph, ac_graph_clean, ac_cleaned_unitigs, ac_cleaned_links, ac_cleaned_summary_get_sized, ac_cleaned_free,
+ *      ac_cleaned_merge_plan, ac_cleaned_finish, ac_cleaned_gfa_string, ac_parse_tig_numbers, ac_gfa_segment_types, ac_clean_gfa, ac_clean
+ *      with ac_cleaned_summary and the AC_CLEAN_* values. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
