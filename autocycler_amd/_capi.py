@@ -172,6 +172,21 @@ class CleanedSummary(C.Structure):      # ac_cleaned_summary
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("size", "reserved")}
 
 
+class TrimmedRecord(C.Structure):      # ac_trimmed_record
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32), ("length", C.c_uint64), ("trimmed", C.c_uint32), ("excluded", C.c_uint32)]
+
+
+class TrimmedSummary(C.Structure):      # ac_trimmed_summary
+    _fields_ = [("size", C.c_uint32), ("chosen", C.c_uint32), ("c_se", C.c_uint32), ("c_hp", C.c_uint32), ("sequences", C.c_uint32), ("trimmed", C.c_uint32),
+                ("excluded", C.c_uint32), ("rejected", C.c_uint32), ("unitigs_in", C.c_uint32), ("unitigs_alive", C.c_uint32), ("launches", C.c_uint32),
+                ("read_backs", C.c_uint32), ("median", C.c_uint64), ("mad", C.c_uint64), ("min_length", C.c_uint64), ("max_length", C.c_uint64),
+                ("entries_kept", C.c_uint64), ("links", C.c_uint64), ("seconds_device", C.c_double), ("align_launches", C.c_uint32), ("reserved", C.c_uint32),
+                ("align_cells", C.c_uint64), ("align_seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("size", "reserved")}
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -230,7 +245,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_clean_graph", "ac_graph_clean", "ac_cleaned_unitigs", "ac_cleaned_links", "ac_cleaned_summary_get_sized", "ac_cleaned_free", "ac_cleaned_merge_plan", "ac_cleaned_finish", "ac_cleaned_gfa_string", "ac_parse_tig_numbers", "ac_gfa_segment_types", "ac_clean_gfa", "ac_clean", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_clean_graph", "ac_graph_clean", "ac_cleaned_unitigs", "ac_cleaned_links", "ac_cleaned_summary_get_sized", "ac_cleaned_free", "ac_cleaned_merge_plan", "ac_cleaned_finish", "ac_cleaned_gfa_string", "ac_parse_tig_numbers", "ac_gfa_segment_types", "ac_clean_gfa", "ac_clean", "ac_trim_apply", "ac_graph_trim_apply", "ac_graph_trim", "ac_trimmed_records", "ac_trimmed_summary_get_sized", "ac_trimmed_free", "ac_trimmed_subsets", "ac_trimmed_finish", "ac_trimmed_yaml_string", "ac_trim_gfa", "ac_trim_dir", "ac_resolve_dir", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -416,6 +431,23 @@ def load_library(path=None):
     lib.ac_gfa_segment_types.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
     lib.ac_clean_gfa.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.ac_clean.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
+    lib.ac_trim_apply.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                  C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_graph_trim_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_graph_trim.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_trimmed_records.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TrimmedRecord)), C.POINTER(C.c_uint32)]
+    lib.ac_trimmed_summary_get_sized.restype = C.c_size_t
+    lib.ac_trimmed_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(TrimmedSummary), C.c_size_t]
+    lib.ac_trimmed_free.restype = None
+    lib.ac_trimmed_free.argtypes = [C.c_void_p]
+    lib.ac_trimmed_subsets.restype = C.c_void_p
+    lib.ac_trimmed_subsets.argtypes = [C.c_void_p]
+    lib.ac_trimmed_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_trimmed_yaml_string.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_trim_gfa.argtypes = [C.c_char_p, C.c_uint64, C.c_double, C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                C.POINTER(TrimmedSummary)]
+    lib.ac_trim_dir.argtypes = [C.c_char_p, C.c_double, C.c_uint32, C.c_double, C.c_int]
+    lib.ac_resolve_dir.argtypes = [C.c_char_p, C.c_int]
     lib.ac_resolve_graphs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
     lib.ac_cluster_tree_from_nodes.argtypes = [C.POINTER(ClusterNode), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ac_cluster_nodes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterNode)), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
@@ -598,6 +630,20 @@ class Graph:
         sm = TrimSummary(size=C.sizeof(TrimSummary))
         _check(self._lib, self._lib.ac_trim_paths(self._h, min_identity, max_unitigs, device, out, C.byref(sm)))
         return [out[i].as_dict() for i in range(n)], sm.as_dict()
+
+    def trim(self, min_identity=0.75, max_unitigs=5000, mad=5.0, device=0):
+        """ac_graph_trim: trim.rs:45-49 on this graph — the alignments, choose_trim_type, the slices, exclude_outliers_in_length and the
+        sequence subset of clean_up_graph — as a Trimmed (which keeps the graph alive)."""
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_graph_trim(self._h, min_identity, max_unitigs, mad, device, C.byref(h)))
+        return Trimmed(self._lib, h, self.unitig_count, (self,))
+
+    def trim_apply(self, results, chosen="auto", mad=5.0, device=0):
+        """ac_graph_trim_apply: the same from a table of slices (trim_paths' list of dicts)."""
+        res = _trim_results(results, self._lib.ac_graph_seq_count(self._h))
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_graph_trim_apply(self._h, res, TRIM_CHOOSE[chosen], mad, device, C.byref(h)))
+        return Trimmed(self._lib, h, self.unitig_count, (self,))
 
     def resolve_bridges(self, device=0):
         """The compute of `autocycler resolve` up to the graph edits (ac_resolve_bridges) on this graph's paths, unitig lengths and
@@ -1115,9 +1161,9 @@ class Subsets:
                    merge_plan_from_links
     summary        dict (clusters, sequences_kept, n_unitigs, entries_kept, unitigs, links, launches, read_backs, seconds_device)"""
 
-    def __init__(self, lib, h, n_unitigs, keepalive):
+    def __init__(self, lib, h, n_unitigs, keepalive, owns=True):
         import numpy as np
-        self._lib, self._h, self.n_unitigs, self._keepalive = lib, h, n_unitigs, keepalive
+        self._lib, self._h, self.n_unitigs, self._keepalive, self._owns = lib, h, n_unitigs, keepalive, owns
         dt = np.dtype([("seqs", "<u4"), ("unitigs", "<u4"), ("entries", "<u8"), ("links", "<u8"), ("length", "<u8")], align=True)
         assert dt.itemsize == C.sizeof(SubsetCluster)
         rp, rn = C.POINTER(SubsetCluster)(), C.c_uint32()
@@ -1146,9 +1192,9 @@ class Subsets:
         self.summary = sm.as_dict()
 
     def close(self):
-        if self._h:
+        if self._h and self._owns:      # (a Trimmed's view is borrowed)
             self._lib.ac_subsets_free(self._h)
-            self._h = None
+        self._h = None
         self._keepalive = None
 
     def __del__(self):
@@ -1234,6 +1280,148 @@ class Subsets:
                                                       sb.ctypes.data if sb is not None else None, sg.ctypes.data if sg is not None else None,
                                                       1 if renumber else 0, device, C.byref(h)))
         return Finished(self._lib, h)
+
+
+TRIM_CHOOSE = {"auto": 0, "none": 1, None: 1, "start_end": 2, "hairpin": 3}
+TRIM_KINDS = {0: None, 1: "start_end", 2: "hairpin"}
+
+
+def _trim_results(results, n_seqs):
+    """a list of trim_paths' result dicts (or None) as an array of ac_trim_result"""
+    if results is None:
+        return None
+    if len(results) != n_seqs:
+        raise AutocyclerError(f"results: one per sequence expected ({n_seqs}), got {len(results)}")
+    out = (TrimResult * max(n_seqs, 1))()
+    for i, r in enumerate(results):
+        for kind in ("start_end", "hairpin"):
+            sl = getattr(out[i], kind)
+            sl.status, sl.begin, sl.end, sl.trimmed_length = (r[kind][f] for f in ("status", "begin", "end", "trimmed_length"))
+        out[i].hairpin_start_trimmed, out[i].hairpin_end_trimmed = r.get("hairpin_start_trimmed", 0), r.get("hairpin_end_trimmed", 0)
+    return out
+
+
+class Trimmed:
+    """Owning handle of an ac_trimmed: a graph's sequences after choose_trim_type and exclude_outliers_in_length, and what they keep of it.
+    records   structured array, one per input sequence: begin, end (the slice of its path that stays), length (new), trimmed, excluded
+    summary   dict: chosen (None, "start_end", "hairpin"), c_se, c_hp, sequences, trimmed, excluded, rejected, unitigs_in, unitigs_alive,
+              launches, read_backs, median, mad, min_length, max_length, entries_kept, links, seconds_device, align_*
+    subsets   a Subsets view with one cluster that does not own: unitigs(1), links(1), merge_plan(1), ... as for any Subsets
+    finish()  merge plan, merged paths and finish with renumbering in one call: a Finished
+    yaml()    2_trimmed.yaml as bytes"""
+
+    def __init__(self, lib, h, n_unitigs, keepalive):
+        import numpy as np
+        self._lib, self._h, self.n_unitigs, self._keepalive = lib, h, n_unitigs, keepalive
+        dt = np.dtype([("begin", "<u4"), ("end", "<u4"), ("length", "<u8"), ("trimmed", "<u4"), ("excluded", "<u4")], align=True)
+        assert dt.itemsize == C.sizeof(TrimmedRecord)
+        rp, rn = C.POINTER(TrimmedRecord)(), C.c_uint32()
+        _check(lib, lib.ac_trimmed_records(h, C.byref(rp), C.byref(rn)))
+        self.records = _take(rp, rn.value, dt)
+        sm = TrimmedSummary()
+        assert lib.ac_trimmed_summary_get_sized(h, C.byref(sm), C.sizeof(TrimmedSummary)) == C.sizeof(TrimmedSummary) == sm.size
+        self.summary = sm.as_dict()
+        self.summary["chosen"] = TRIM_KINDS[sm.chosen]
+        self.subsets = Subsets(lib, C.c_void_p(lib.ac_trimmed_subsets(h)), n_unitigs, None, owns=False)
+
+    def close(self):
+        if self._h:
+            self.subsets._h = None      # (borrowed: it dies with this object)
+            self._lib.ac_trimmed_free(self._h)
+            self._h = None
+        self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def kept(self):
+        """the indices of the sequences that stay, ascending"""
+        return [i for i, x in enumerate(self.records["excluded"].tolist()) if not x]
+
+    def finish(self, sequences=None, device=0):
+        """ac_trimmed_finish.  sequences: (all bytes as a uint8 array, the first byte of every unitig as a uint64 array) for an object made
+        from plain arrays; None on one made from a Graph."""
+        import numpy as np
+        sb = sg = None
+        if sequences is not None:
+            sb, sg = np.ascontiguousarray(sequences[0], dtype=np.uint8), np.ascontiguousarray(sequences[1], dtype=np.uint64)
+            if sg.shape != (self.n_unitigs,):
+                raise AutocyclerError(f"sequences[1]: one entry per unitig expected ({self.n_unitigs}), got shape {sg.shape}")
+        h = C.c_void_p()
+        _check(self._lib, self._lib.ac_trimmed_finish(self._h, sb.ctypes.data if sb is not None else None, sg.ctypes.data if sg is not None else None, device,
+                                                      C.byref(h)))
+        return Finished(self._lib, h)
+
+    def yaml(self):
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.ac_trimmed_yaml_string(self._h, C.byref(out), C.byref(n)))
+        text = C.string_at(out.value, n.value)
+        self._lib.ac_string_free(out)
+        return text
+
+
+def trim_apply(n_unitigs, links, unitig_len, paths, seq_lengths, results, chosen="auto", mad=5.0, alive=None, unitig_type=None, device=0, lib_path=None):
+    """ac_trim_apply: trim's edit on plain arrays.  links, unitig_len, paths, alive as for subsets_from_paths; seq_lengths: one per sequence;
+    results: trim_path_slices' list of dicts (None with chosen="none"); unitig_type: AC_UNITIG_* bytes or None."""
+    import numpy as np
+    lib = load_library(lib_path)
+    la = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1, 2))
+    ln = np.ascontiguousarray(np.asarray(unitig_len, dtype=np.uint32))
+    if ln.shape != (n_unitigs,):
+        raise AutocyclerError(f"unitig_len: one entry per unitig expected ({n_unitigs}), got shape {ln.shape}")
+    al, ty = _bytes_per_unitig(alive, n_unitigs, "alive"), _bytes_per_unitig(unitig_type, n_unitigs, "unitig_type")
+    if isinstance(paths, tuple):
+        ent, off = np.ascontiguousarray(paths[0], dtype=np.int32), np.ascontiguousarray(paths[1], dtype=np.uint64)
+    else:
+        ent = np.ascontiguousarray(np.fromiter((e for p in paths for e in p), dtype=np.int32))
+        off = np.zeros(len(paths) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64) if len(paths) else []
+    n_seqs = off.shape[0] - 1
+    sl = np.ascontiguousarray(np.asarray(seq_lengths, dtype=np.uint32))
+    if sl.shape != (n_seqs,):
+        raise AutocyclerError(f"seq_lengths: one per sequence expected ({n_seqs}), got shape {sl.shape}")
+    res = _trim_results(results, n_seqs)
+    if ln.size == 0:
+        ln = np.zeros(1, dtype=np.uint32)
+    if sl.size == 0:
+        sl = np.zeros(1, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_trim_apply(n_unitigs, ptr(la), la.shape[0], ptr(ln), ptr(al), ptr(ty), ptr(ent), off.ctypes.data, ptr(sl), n_seqs, res, TRIM_CHOOSE[chosen],
+                                  mad, device, C.byref(h)))
+    return Trimmed(lib, h, n_unitigs, (la, ln, al, ty, ent, off, sl))
+
+
+def trim_gfa(text, min_identity=0.75, max_unitigs=5000, mad=5.0, device=0, lib_path=None):
+    """ac_trim_gfa: `autocycler trim` from the text of 1_untrimmed.gfa (segment numbers in any order) -> (2_trimmed.gfa as bytes,
+    2_trimmed.yaml as bytes, summary dict)"""
+    lib = load_library(lib_path)
+    b = text.encode() if isinstance(text, str) else text
+    gfa, n, yaml, sm = C.c_void_p(), C.c_uint64(), C.c_void_p(), TrimmedSummary()
+    sm.size = C.sizeof(TrimmedSummary)
+    _check(lib, lib.ac_trim_gfa(b, len(b), min_identity, max_unitigs, mad, device, C.byref(gfa), C.byref(n), C.byref(yaml), C.byref(sm)))
+    out = C.string_at(gfa.value, n.value), C.string_at(yaml.value)
+    lib.ac_string_free(gfa)
+    lib.ac_string_free(yaml)
+    d = sm.as_dict()
+    d["chosen"] = TRIM_KINDS[sm.chosen]
+    return out[0], out[1], d
+
+
+def trim_dir(cluster_dir, min_identity=0.75, max_unitigs=5000, mad=5.0, device=0, lib_path=None):
+    """ac_trim_dir: <cluster_dir>/1_untrimmed.gfa -> 2_trimmed.gfa, 2_trimmed.yaml"""
+    lib = load_library(lib_path)
+    _check(lib, lib.ac_trim_dir(str(cluster_dir).encode(), min_identity, max_unitigs, mad, device))
+
+
+def resolve_dir(cluster_dir, device=0, lib_path=None):
+    """ac_resolve_dir: <cluster_dir>/2_trimmed.gfa -> 3_bridged.gfa, 4_merged.gfa, 5_final.gfa"""
+    lib = load_library(lib_path)
+    _check(lib, lib.ac_resolve_dir(str(cluster_dir).encode(), device))
 
 
 class Finished:

@@ -316,4 +316,48 @@ int ac_compress_dir_multi(const char* assemblies_dir, const char* autocycler_dir
     });
 }
 
+// ---- `trim` and `resolve` as commands on a cluster directory: the text entries of capi_steps.cpp between a read and write_pieces ----
+namespace fs = std::filesystem;
+static std::string read_cluster_file(const fs::path& dir, const char* name) {
+    if (!fs::is_directory(dir)) throw UserError("directory does not exist: " + dir.string());
+    const fs::path p = dir / name;
+    std::ifstream f(p, std::ios::binary);
+    if (!f) throw UserError("file does not exist: " + p.string());
+    return std::string(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+}
+struct OwnedText {
+    char* p = nullptr;
+    ~OwnedText() { free(p); }
+    std::string str() const { return p ? std::string(p) : std::string(); }
+};
+// trim.rs:36-53
+int ac_trim_dir(const char* cluster_dir, double min_identity, uint32_t max_unitigs, double mad, int device) {
+    return guarded([&] {
+        if (!cluster_dir) throw DeviceError("null pointer: cluster_dir");
+        const fs::path dir(cluster_dir);
+        const std::string text = read_cluster_file(dir, "1_untrimmed.gfa");
+        OwnedText gfa, yaml;
+        if (ac_trim_gfa(text.data(), text.size(), min_identity, max_unitigs, mad, device, &gfa.p, nullptr, &yaml.p, nullptr) != 0) throw DeviceError(last_error());
+        write_pieces((dir / "2_trimmed.gfa").string(), {gfa.str()}, 1);
+        write_pieces((dir / "2_trimmed.yaml").string(), {yaml.str()}, 1);
+    });
+}
+// resolve.rs:41-67 (without --verbose): 2_trimmed.gfa is renumbered, so load_gfa reads it
+int ac_resolve_dir(const char* cluster_dir, int device) {
+    return guarded([&] {
+        if (!cluster_dir) throw DeviceError("null pointer: cluster_dir");
+        const fs::path dir(cluster_dir);
+        const std::string text = read_cluster_file(dir, "2_trimmed.gfa");
+        ac_graph* gp = nullptr;
+        if (ac_graph_from_gfa(text.data(), text.size(), &gp) != 0) throw DeviceError(last_error());
+        std::unique_ptr<ac_graph> g(gp);
+        OwnedText bridged, merged, final_text;
+        uint32_t culled = 0;
+        if (ac_resolve_graphs(g.get(), device, &bridged.p, &merged.p, &final_text.p, &culled) != 0) throw DeviceError(last_error());
+        write_pieces((dir / "3_bridged.gfa").string(), {bridged.str()}, 1);
+        write_pieces((dir / "4_merged.gfa").string(), {merged.str()}, 1);
+        write_pieces((dir / "5_final.gfa").string(), {final_text.str()}, 1);
+    });
+}
+
 }  // extern "C"

@@ -436,6 +436,7 @@ struct ac_subsets {
     // borrowed from the caller until ac_subsets_free
     const ac_link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const int32_t* path = nullptr; const uint64_t* path_off = nullptr;
     const ac_graph* graph = nullptr;
+    const uint8_t* type = nullptr;      // AC_UNITIG_* per unitig, or null = Other: only an ac_trimmed's view carries any
 };
 struct ac_merged_paths {
     MergedPathsResult r;
@@ -569,7 +570,7 @@ int ac_subsets_merge_plan(const ac_subsets* s, uint32_t cluster, const uint8_t* 
             for (uint32_t u = 0; u < n; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + s->unitig_len[u]);
         const uint64_t l0 = s->r.link_off[cluster - 1], l1 = s->r.link_off[cluster], e0 = s->r.ends_off[cluster - 1], e1 = s->r.ends_off[cluster];
         merge_run(n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), s->r.path_ends.data() + 2 * e0, (uint32_t)(e1 - e0), depth.data(),
-                  positions.data(), positions.data(), nullptr, seq_bytes, seq_begin, seq_total, nullptr, 0, device, out);
+                  positions.data(), positions.data(), s->type, seq_bytes, seq_begin, seq_total, nullptr, 0, device, out);
         (*out)->cluster = cluster;
     });
 }
@@ -687,7 +688,7 @@ int ac_subsets_finish(const ac_subsets* s, uint32_t cluster, const ac_merge* pla
         } else if (seq_bytes)
             for (uint32_t u = 0; u < n; u++) seq_total = std::max<uint64_t>(seq_total, seq_begin[u] + s->unitig_len[u]);
         const uint64_t l0 = s->r.link_off[cluster - 1], l1 = s->r.link_off[cluster];
-        finish_run(plan, n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), depth.data(), nullptr, seq_bytes, seq_begin, seq_total, merged_paths,
+        finish_run(plan, n, (const ac_link*)s->r.links.data() + l0, l1 - l0, s->unitig_len, alive.data(), depth.data(), s->type, seq_bytes, seq_begin, seq_total, merged_paths,
                    renumber, device, out);
     });
 }
@@ -1164,6 +1165,194 @@ int ac_clean(const char* in_gfa, const char* out_gfa, const char* remove, const 
         o.write(out.data(), (std::streamsize)out.size());
         o.close();
         if (!o) throw DeviceError(std::string("failed to write ") + out_gfa);
+    });
+}
+
+// ---- `autocycler trim`, the edit: choose_trim_type's slices, their length check, exclude_outliers_in_length and clean_up_graph's subset on the
+// device (kernels_trim_apply.inc, then the stages of kernels_subset.inc on the same entries); the choice, the statistics and the yaml on the host
+// (trim_apply_host.cpp).  The object owns a one-cluster ac_subsets: merge plan, merged paths and finish are the subsets' own ----
+struct ac_trimmed {
+    ac_subsets sub;      // path / path_off: the slices below
+    TrimApplyPlan tp;
+    ac_trimmed_summary summary;
+};
+static_assert(sizeof(ac_trimmed_record) == sizeof(TrimApplyRecord) && offsetof(ac_trimmed_record, length) == offsetof(TrimApplyRecord, length) &&
+              offsetof(ac_trimmed_record, excluded) == offsetof(TrimApplyRecord, excluded), "ac_trimmed_record and TrimApplyRecord are one layout");
+static_assert(AC_TRIM_CHOOSE_AUTO == TRIM_CHOOSE_AUTO && AC_TRIM_CHOOSE_NONE == TRIM_CHOOSE_NONE && AC_TRIM_CHOOSE_START_END == TRIM_CHOOSE_START_END &&
+              AC_TRIM_CHOOSE_HAIRPIN == TRIM_CHOOSE_HAIRPIN, "the AC_TRIM_CHOOSE_* values are trim_apply_host.hpp's");
+static void trimmed_run(uint32_t n, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* type, const int32_t* path,
+                        const uint64_t* path_off, const uint32_t* seq_length, uint32_t n_seqs, const ac_trim_result* results, uint32_t chosen, double mad,
+                        const ac_graph* graph, const ac_trim_summary* align, int device, std::unique_ptr<ac_trimmed>* out) {
+    if (!path_off) throw DeviceError("null pointer: path_off");
+    if (!seq_length) throw DeviceError("null pointer: seq_length");
+    if (n && !unitig_len) throw DeviceError("null pointer: unitig_len");
+    if (n_links && !links) throw DeviceError("null pointer: n_links > 0 without links");
+    if (mad < 0.0) throw DeviceError("--mad cannot be less than 0");
+    auto h = std::make_unique<ac_trimmed>();
+    TrimApplyPlan& tp = h->tp;
+    std::vector<TrimResult> res(results ? n_seqs : 0);
+    for (size_t s = 0; s < res.size(); s++) {
+        const ac_trim_result& r = results[s];
+        res[s].se = TrimSlice{r.start_end.status, r.start_end.begin, r.start_end.end, r.start_end.trimmed_length};
+        res[s].hp = TrimSlice{r.hairpin.status, r.hairpin.begin, r.hairpin.end, r.hairpin.trimmed_length};
+    }
+    trim_apply_choose(results ? res.data() : nullptr, n_seqs, path, path_off, seq_length, chosen, &tp);
+    ac_subsets& sub = h->sub;
+    sub.links = links; sub.n_links = n_links; sub.unitig_len = unitig_len; sub.path = tp.sliced.data(); sub.path_off = tp.sliced_off.data(); sub.graph = graph;
+    sub.type = type;
+    sub.r.n_unitigs = n;
+    const uint64_t ne = tp.sliced_off[n_seqs];
+    if (n == 0 || ne == 0) {      // (no entry anywhere: every sum is 0; no device is asked for)
+        if (ne) throw DeviceError(subset_bad_entry_message(0, tp.seqs[0].begin, tp.sliced[0], n));
+        if (n == 0 && n_links) throw DeviceError(components_bad_link_message(0, links[0].a, links[0].b, 0));
+        for (uint32_t s = 0; s < n_seqs; s++)
+            if (tp.seqs[s].length != 0) throw DeviceError(trim_apply_mismatch_message(s, 0, tp.seqs[s].length));
+        trim_apply_exclude(&tp, mad);
+        subset_prepare(n_seqs, tp.sliced.data(), tp.sliced_off.data(), tp.label.data(), 1, &sub.plan, &sub.r);
+        subset_empty_products(&sub.r);
+    } else {
+        TrimApplyInput in;
+        in.n_unitigs = n; in.links = (const Link*)links; in.n_links = n_links; in.unitig_len = unitig_len; in.alive = alive; in.path = path; in.path_off = path_off;
+        in.mad = mad;
+        DeviceCall call(device);
+        trim_apply_device(in, &tp, &sub.plan, &sub.r);
+    }
+    subset_finish(&sub.r, sub.plan);
+    ac_subsets_summary& ss = sub.summary;
+    memset(&ss, 0, sizeof ss);
+    ss.size = (uint32_t)sizeof ss; ss.clusters = 1; ss.sequences_kept = (uint32_t)sub.plan.kept_seq.size(); ss.n_unitigs = n;
+    ss.entries_kept = sub.r.kept_entries; ss.unitigs = sub.r.unitigs.size(); ss.links = sub.r.links.size();
+    ss.launches = sub.r.stats.launches; ss.read_backs = sub.r.stats.read_backs; ss.seconds_device = sub.r.stats.seconds_device;
+    ac_trimmed_summary& sm = h->summary;
+    memset(&sm, 0, sizeof sm);
+    sm.size = (uint32_t)sizeof sm; sm.chosen = tp.chosen; sm.c_se = tp.c_se; sm.c_hp = tp.c_hp; sm.sequences = n_seqs; sm.trimmed = tp.n_trimmed;
+    sm.excluded = tp.n_excluded; sm.rejected = tp.rejected; sm.unitigs_in = n; sm.unitigs_alive = (uint32_t)sub.r.unitigs.size();
+    sm.launches = sub.r.stats.launches; sm.read_backs = sub.r.stats.read_backs; sm.median = tp.median; sm.mad = tp.mad; sm.min_length = tp.min_length;
+    sm.max_length = tp.max_length; sm.entries_kept = sub.r.kept_entries; sm.links = sub.r.links.size(); sm.seconds_device = sub.r.stats.seconds_device;
+    if (align) { sm.align_launches = align->launches; sm.align_cells = align->cells; sm.align_seconds_device = align->seconds_device; }
+    *out = std::move(h);
+}
+static const ac_graph* trimmed_check_graph(const ac_graph* g) {
+    if (!g) throw DeviceError("null pointer");
+    if (!g->host_arrays || !g->host_paths) throw DeviceError("this rank kept no host arrays (sharded build, not the writing rank)");
+    const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+    if (n_seqs == 0 || g->g.path_off.size() != (size_t)n_seqs + 1 || !g->g.seq_len) throw DeviceError("trim: the graph holds no paths");
+    return g;
+}
+static void trimmed_on_graph(const ac_graph* g, const uint8_t* type, const ac_trim_result* results, uint32_t chosen, double mad, const ac_trim_summary* align, int device,
+                             std::unique_ptr<ac_trimmed>* out) {
+    const FinalGraph& f = g->g;
+    trimmed_run(f.n_unitigs, (const ac_link*)f.links, f.n_links, f.seq_len, nullptr, type, f.path, f.path_off.data(), g->seq_lens.data(), (uint32_t)g->seq_ids.size(),
+                results, chosen, mad, g, align, device, out);
+}
+// trim_start_end_overlap, trim_harpin_overlap, then the edit with choose_trim_type's own choice
+static void trimmed_whole(const ac_graph* g, const uint8_t* type, double min_identity, uint32_t max_unitigs, double mad, int device, std::unique_ptr<ac_trimmed>* out) {
+    trim_apply_check_settings(min_identity, mad);
+    const uint32_t n_seqs = (uint32_t)g->seq_ids.size();
+    std::vector<ac_trim_result> results(n_seqs);
+    ac_trim_summary align;
+    memset(&align, 0, sizeof align);
+    align.size = sizeof align;
+    trim_slices(g->g.path, g->g.path_off.data(), n_seqs, g->g.seq_len, g->g.n_unitigs, min_identity, max_unitigs, device, results.data(), &align);
+    trimmed_on_graph(g, type, results.data(), AC_TRIM_CHOOSE_AUTO, mad, &align, device, out);
+}
+int ac_trim_apply(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive, const uint8_t* type,
+                  const int32_t* path_entries, const uint64_t* path_off, const uint32_t* seq_length, uint32_t n_seqs, const ac_trim_result* results, uint32_t chosen,
+                  double mad, int device, ac_trimmed** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        std::unique_ptr<ac_trimmed> h;
+        trimmed_run(n_unitigs, links, n_links, unitig_len, alive, type, path_entries, path_off, seq_length, n_seqs, results, chosen, mad, nullptr, nullptr, device, &h);
+        *out = h.release();
+    });
+}
+int ac_graph_trim_apply(const ac_graph* g, const ac_trim_result* results, uint32_t chosen, double mad, int device, ac_trimmed** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        std::unique_ptr<ac_trimmed> h;
+        trimmed_on_graph(trimmed_check_graph(g), nullptr, results, chosen, mad, nullptr, device, &h);
+        *out = h.release();
+    });
+}
+int ac_graph_trim(const ac_graph* g, double min_identity, uint32_t max_unitigs, double mad, int device, ac_trimmed** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        std::unique_ptr<ac_trimmed> h;
+        trimmed_whole(trimmed_check_graph(g), nullptr, min_identity, max_unitigs, mad, device, &h);
+        *out = h.release();
+    });
+}
+int ac_trimmed_records(const ac_trimmed* t, const ac_trimmed_record** records, uint32_t* n_seqs) {
+    return guarded([&] {
+        if (!t || !records || !n_seqs) throw DeviceError("null pointer");
+        *records = (const ac_trimmed_record*)t->tp.seqs.data(); *n_seqs = (uint32_t)t->tp.seqs.size();
+    });
+}
+size_t ac_trimmed_summary_get_sized(const ac_trimmed* t, ac_trimmed_summary* out, size_t out_size) {
+    if (t && out) memcpy(out, &t->summary, std::min(out_size, sizeof(ac_trimmed_summary)));
+    return sizeof(ac_trimmed_summary);
+}
+void ac_trimmed_free(ac_trimmed* t) { delete t; }
+const ac_subsets* ac_trimmed_subsets(const ac_trimmed* t) { return t ? &t->sub : nullptr; }
+static void trimmed_finish(const ac_trimmed* t, const uint8_t* seq_bytes, const uint64_t* seq_begin, int device, ac_finished** out) {
+    struct Free {
+        void operator()(ac_merge* p) const { ac_merge_free(p); }
+        void operator()(ac_merged_paths* p) const { ac_merged_paths_free(p); }
+    };
+    ac_merge* mp = nullptr;
+    if (ac_subsets_merge_plan(&t->sub, 1, seq_bytes, seq_begin, 1, device, &mp)) throw DeviceError(last_error());
+    std::unique_ptr<ac_merge, Free> m(mp);
+    ac_merged_paths* pp = nullptr;
+    if (ac_subsets_merged_paths(&t->sub, 1, m.get(), device, &pp)) throw DeviceError(last_error());
+    std::unique_ptr<ac_merged_paths, Free> p(pp);
+    if (ac_subsets_finish(&t->sub, 1, m.get(), p.get(), seq_bytes, seq_begin, 1, device, out)) throw DeviceError(last_error());
+}
+int ac_trimmed_finish(const ac_trimmed* t, const uint8_t* seq_bytes, const uint64_t* seq_begin, int device, ac_finished** out) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!t) throw DeviceError("null pointer");
+        trimmed_finish(t, seq_bytes, seq_begin, device, out);
+    });
+}
+int ac_trimmed_yaml_string(const ac_trimmed* t, char** out, uint64_t* len) {
+    return guarded([&] {
+        if (!out) throw DeviceError("null pointer: out");
+        *out = nullptr;
+        if (!t) throw DeviceError("null pointer");
+        *out = malloc_string(trim_apply_yaml(t->tp), len);
+    });
+}
+// trim.rs:43-51 from text to texts (capi_command.cpp's ac_trim_dir is the file form)
+int ac_trim_gfa(const char* gfa_text, uint64_t len, double min_identity, uint32_t max_unitigs, double mad, int device, char** gfa, uint64_t* gfa_len, char** yaml,
+                ac_trimmed_summary* summary) {
+    return guarded([&] {
+        if (!gfa || !yaml) throw DeviceError("null pointer: out");
+        *gfa = nullptr; *yaml = nullptr;
+        if (!gfa_text && len) throw DeviceError("null pointer: gfa_text");
+        trim_apply_check_settings(min_identity, mad);
+        auto g = std::make_unique<ac_graph>();
+        std::vector<SeqMeta> meta;
+        std::vector<uint32_t> tags;
+        load_gfa_any_numbers(gfa_text, len, &g->g, &meta, nullptr, &tags);
+        for (auto& m : meta) { g->seq_ids.push_back(m.id); g->seq_lens.push_back(m.length); g->filenames.push_back(m.filename); g->headers.push_back(m.contig_header); }
+        const std::vector<uint8_t> types = clean_gfa_types(gfa_text, len);
+        if (types.size() != g->g.n_unitigs) throw DeviceError("trim: the S lines of the text and the loaded graph disagree (internal error)");
+        std::unique_ptr<ac_trimmed> t;
+        trimmed_whole(trimmed_check_graph(g.get()), types.data(), min_identity, max_unitigs, mad, device, &t);
+        ac_finished* fp = nullptr;
+        trimmed_finish(t.get(), nullptr, nullptr, device, &fp);
+        std::unique_ptr<ac_finished, void (*)(ac_finished*)> f(fp, ac_finished_free);
+        std::vector<FinishSeqMeta> kept;      // save_gfa's P lines: the kept sequences in input order, with their new lengths
+        for (uint32_t s : f->r.path_seq) kept.push_back(FinishSeqMeta{meta[s].id, (uint32_t)t->tp.seqs[s].length, meta[s].filename, meta[s].contig_header, tags[s]});
+        char* text = malloc_string(finish_gfa_string(f->r, g->g.k, kept, false), gfa_len);
+        try { *yaml = malloc_string(trim_apply_yaml(t->tp), nullptr); }
+        catch (...) { free(text); throw; }
+        *gfa = text;
+        if (summary) memcpy(summary, &t->summary, std::min<size_t>(summary->size, sizeof(ac_trimmed_summary)));
     });
 }
 

@@ -2,7 +2,7 @@
 //   -i/--assemblies_dir DIR  -a/--autocycler_dir DIR  [--kmer 51] [--max_contigs 25] [-t/--threads 8] [--device 0 | --devices 0,1,..] [--stats]
 // (--devices: one job over several GPUs of the node through ac_compress_build_multi; --stats: the graph's connected components and
 // topology after the usual lines, ac_graph_components; neither is a flag of the reference)
-// Two more commands sit next to it: `decompress` and `clean` (below).
+// Four more commands sit next to it: `decompress`, `clean`, `trim` and `resolve` (below).
 // Writes DIR/input_assemblies.gfa and DIR/input_assemblies.yaml (compress.rs:45-46) through the C ABI
 // (ac_compress_dir: C++ loader + end repair, HIP graph build, host tail, buffered GFA writer).
 #include <chrono>
@@ -17,6 +17,10 @@
 
 static void usage() {
     fprintf(stderr, "Usage: autocycler-compress --assemblies_dir <DIR> --autocycler_dir <DIR> [--kmer 51] [--max_contigs 25] [--threads 8] [--device 0 | --devices 0,1,..] [--stats]\n");
+    fprintf(stderr, "       autocycler-compress decompress --in_gfa <GFA> [--out_dir <DIR>] [--out_file <FASTA>]\n");
+    fprintf(stderr, "       autocycler-compress clean --in_gfa <GFA> --out_gfa <GFA> [--remove <TIGS>] [--duplicate <TIGS>] [--min_depth <DEPTH>] [--device 0]\n");
+    fprintf(stderr, "       autocycler-compress trim --cluster_dir <DIR> [--min_identity 0.75] [--max_unitigs 5000] [--mad 5.0] [--device 0]\n");
+    fprintf(stderr, "       autocycler-compress resolve --cluster_dir <DIR> [--device 0]\n");
 }
 
 // `autocycler decompress` (main.rs:163-175): -i/--in_gfa FILE  [-o/--out_dir DIR]  [-f/--out_file FASTA]
@@ -79,8 +83,50 @@ static int clean_main(int argc, char** argv) {
     return 0;
 }
 
+// `autocycler trim` (main.rs: Trim): -c/--cluster_dir DIR  [--min_identity 0.75]  [--max_unitigs 5000]  [--mad 5.0]  [--device 0]
+// `autocycler resolve` (main.rs: Resolve): -c/--cluster_dir DIR  [--device 0]   (--verbose is not offered)
+static int cluster_dir_main(int argc, char** argv, bool trim) {
+    std::string dir;
+    double min_identity = 0.75, mad = 5.0;
+    unsigned max_unitigs = 5000;
+    int device = 0;
+    const char* use = trim ? "Usage: autocycler-compress trim --cluster_dir <DIR> [--min_identity 0.75] [--max_unitigs 5000] [--mad 5.0] [--device 0]\n"
+                           : "Usage: autocycler-compress resolve --cluster_dir <DIR> [--device 0]\n";
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto val = [&]() -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", a.c_str()); exit(2); }
+            return argv[++i];
+        };
+        auto real = [&](const char* v, double* out) {
+            char* end = nullptr;
+            *out = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v, a.c_str()); exit(2); }
+        };
+        if (a == "-c" || a == "--cluster_dir") dir = val();
+        else if (trim && a == "--min_identity") real(val(), &min_identity);
+        else if (trim && a == "--max_unitigs") max_unitigs = (unsigned)strtoul(val(), nullptr, 10);
+        else if (trim && a == "--mad") real(val(), &mad);
+        else if (a == "--device") device = atoi(val());
+        else { fprintf(stderr, "error: unexpected argument '%s'\n%s", a.c_str(), use); return 2; }
+    }
+    if (dir.empty()) { fprintf(stderr, "%s", use); return 2; }
+    fprintf(stderr, "\nStarting autocycler %s\nSettings:\n  --cluster_dir %s\n", trim ? "trim" : "resolve", dir.c_str());
+    if (trim) fprintf(stderr, "  --min_identity %g\n  --max_unitigs %u\n  --mad %g\n", min_identity, max_unitigs, mad);
+    const int rc = trim ? ac_trim_dir(dir.c_str(), min_identity, max_unitigs, mad, device) : ac_resolve_dir(dir.c_str(), device);
+    if (rc != 0) {
+        fprintf(stderr, "\nError: %s\n", ac_last_error());
+        return 1;
+    }
+    if (trim) fprintf(stderr, "\nFinished!\nTrimmed graph: %s/2_trimmed.gfa\n\n", dir.c_str());
+    else fprintf(stderr, "\nFinished!\nFinal graph: %s/5_final.gfa\n\n", dir.c_str());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "decompress") == 0) return decompress_main(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "trim") == 0) return cluster_dir_main(argc, argv, true);
+    if (argc > 1 && strcmp(argv[1], "resolve") == 0) return cluster_dir_main(argc, argv, false);
     if (argc > 1 && strcmp(argv[1], "clean") == 0) return clean_main(argc, argv);
     std::string in, out;
     unsigned k = 51, max_contigs = 25;

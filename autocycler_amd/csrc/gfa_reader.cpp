@@ -8,6 +8,7 @@
 #include <cstring>
 #include <numeric>
 #include <stdexcept>
+#include <unordered_map>
 
 namespace ac {
 
@@ -39,11 +40,17 @@ uint64_t to_u64(const char* s, size_t n, const char* what) {
 }
 }  // namespace
 
-void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs) {
+// numbers == nullptr: the segments must be numbered 1, 2, 3, ... in order.  Otherwise any distinct positive numbers are taken, mapped to 1..n in
+// file order (the table goes to *numbers), and cluster_tags receives every P line's CL:i tag (0 without one).
+static void load_gfa_impl(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs, std::vector<uint64_t>* numbers, std::vector<uint32_t>* cluster_tags) {
+    std::unordered_map<uint64_t, uint32_t> index_of;      // a segment's number -> its place in the file, 1-based
+    std::vector<std::pair<uint64_t, uint64_t>> raw_links; // the L lines' own numbers, beside `links`
+    if (numbers) numbers->clear();
+    if (cluster_tags) cluster_tags->clear();
     struct Seg { const char* seq; size_t n; double depth; };
     std::vector<Seg> segs;
     std::vector<Link> links;
-    struct PathLine { uint64_t id; const char* p; size_t n; uint64_t ln; std::string fn, hd; };
+    struct PathLine { uint64_t id; const char* p; size_t n; uint64_t ln; std::string fn, hd; uint64_t cl = 0; };
     std::vector<PathLine> paths;
     uint32_t k = 0;
     size_t a = 0;
@@ -61,7 +68,11 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
                 case 'S': {   // Unitig::from_segment_line (unitig.rs:63-92): number, sequence, DP:f tag required
                     if (f.size() < 3) throw GfaError("segment line does not have enough parts");
                     uint64_t number = to_u64(f[1].first, f[1].second, "unitig number");
-                    if (number != segs.size() + 1)
+                    if (numbers) {
+                        if (number == 0) throw GfaError("segment number 0 in the GFA segment line");
+                        if (!index_of.emplace(number, (uint32_t)segs.size() + 1).second) throw GfaError("segment " + std::to_string(number) + " occurs twice in the GFA");
+                        numbers->push_back(number);
+                    } else if (number != segs.size() + 1)
                         throw GfaError("this loader reads GFAs as `autocycler compress` writes them: segments numbered 1, 2, 3, ... in order");
                     double depth = -1;
                     for (size_t i = 3; i < f.size(); i++)
@@ -74,8 +85,9 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
                     if (f.size() < 6 || f[5].second != 2 || memcmp(f[5].first, "0M", 2))
                         throw GfaError("non-zero overlap found on the GFA link line.\nAre you sure this is an Autocycler-generated GFA file?");
                     // (numbers beyond what a signed entry holds name no unitig of a graph this library can hold: kept as 0x7FFFFFFF, refused below)
-                    const uint64_t na = std::min<uint64_t>(to_u64(f[1].first, f[1].second, "segment 1 as integer"), 0x7FFFFFFFu);
-                    const uint64_t nb = std::min<uint64_t>(to_u64(f[3].first, f[3].second, "segment 2 as integer"), 0x7FFFFFFFu);
+                    uint64_t na = to_u64(f[1].first, f[1].second, "segment 1 as integer"), nb = to_u64(f[3].first, f[3].second, "segment 2 as integer");
+                    if (numbers) { raw_links.push_back({na, nb}); na = nb = 1; }      // (mapped below, when every S line has been read)
+                    na = std::min<uint64_t>(na, 0x7FFFFFFFu); nb = std::min<uint64_t>(nb, 0x7FFFFFFFu);
                     if (na == 0) throw GfaError("link refers to nonexistent unitig: 0");
                     if (nb == 0) throw GfaError("link refers to nonexistent unitig: 0");
                     Link l;
@@ -94,6 +106,7 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
                         if (f[i].second > 5 && !memcmp(f[i].first, "LN:i:", 5)) pl.ln = to_u64(f[i].first + 5, f[i].second - 5, "LN:i");
                         else if (f[i].second >= 5 && !memcmp(f[i].first, "FN:Z:", 5)) { pl.fn.assign(f[i].first + 5, f[i].second - 5); has_fn = true; }
                         else if (f[i].second >= 5 && !memcmp(f[i].first, "HD:Z:", 5)) { pl.hd.assign(f[i].first + 5, f[i].second - 5); has_hd = true; }
+                        else if (cluster_tags && f[i].second > 5 && !memcmp(f[i].first, "CL:i:", 5)) pl.cl = to_u64(f[i].first + 5, f[i].second - 5, "CL:i");
                     }
                     if (pl.ln == ~0ULL || !has_fn || !has_hd) throw GfaError("missing required tag in GFA path line.");
                     if (pl.id == 0 || pl.id > 32767) throw GfaError("sequence id out of range in GFA path line");
@@ -123,6 +136,13 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
         off += segs[i].n;
     }
     g->seq_begin = seq_begin; g->depth = depth; g->seq_len = seq_len;
+    for (size_t i = 0; i < raw_links.size(); i++) {
+        const auto a_at = index_of.find(raw_links[i].first), b_at = index_of.find(raw_links[i].second);
+        if (a_at == index_of.end()) throw GfaError("link refers to nonexistent unitig: " + std::to_string(raw_links[i].first));
+        if (b_at == index_of.end()) throw GfaError("link refers to nonexistent unitig: " + std::to_string(raw_links[i].second));
+        links[i].a = links[i].a > 0 ? (int32_t)a_at->second : -(int32_t)a_at->second;
+        links[i].b = links[i].b > 0 ? (int32_t)b_at->second : -(int32_t)b_at->second;
+    }
     // link vectors are per unitig strand in file order; save_gfa walks the unitigs: forward_next, then reverse_next
     for (auto& l : links) {
         if (l.na() == 0 || l.na() > U) throw GfaError("link refers to nonexistent unitig: " + std::to_string(l.na()));
@@ -147,6 +167,11 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
             char st = t.first[t.second - 1];
             if (st != '+' && st != '-') throw GfaError("invalid path strand");
             uint64_t u = to_u64(t.first, t.second - 1, "unitig number in path");
+            if (numbers) {
+                const auto at = index_of.find(u);
+                if (at == index_of.end()) throw GfaError("unitig " + std::to_string(u) + " not found in unitig index");
+                u = at->second;
+            }
             if (u == 0 || u > U) throw GfaError("unitig " + std::to_string(u) + " not found in unitig index");
             ent.push_back(st == '+' ? (int32_t)u : -(int32_t)u);
             sum += seq_len[u - 1];
@@ -154,6 +179,7 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
         if (sum != pl.ln) throw GfaError("Position calculation mismatch");      // unitig_graph.rs:173
         g->path_off.push_back(ent.size());
         seqs->push_back(SeqMeta{(uint16_t)pl.id, (uint32_t)pl.ln, pl.fn, pl.hd});
+        if (cluster_tags) cluster_tags->push_back((uint32_t)std::min<uint64_t>(pl.cl, 0xFFFFFFFFu));
     }
     g->path_block = heap_block(ent.size() * 4);
     if (!ent.empty()) memcpy(g->path_block.p, ent.data(), ent.size() * 4);
@@ -163,6 +189,15 @@ void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>*
     for (auto& l : links) if (l.a == -l.b) self_mirror++;
     GraphStats st{(uint32_t)U, (links.size() + self_mirror) / 2, total};
     g->pre = st; g->post = st;
+}
+
+void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs) { load_gfa_impl(text, len, g, seqs, nullptr, nullptr); }
+
+// The GFAs `cluster` writes (save_cluster_gfa, cluster.rs:794-806: after merge_linear_paths, without renumber_unitigs): the segment numbers have
+// holes and are out of order.  They are mapped to 1..n in file order — graph.unitigs order in the reference — and kept for messages.
+void load_gfa_any_numbers(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs, std::vector<uint64_t>* numbers, std::vector<uint32_t>* cluster_tags) {
+    std::vector<uint64_t> own;
+    load_gfa_impl(text, len, g, seqs, numbers ? numbers : &own, cluster_tags);
 }
 
 // reconstruct_original_sequences (unitig_graph.rs:362-388) for one sequence: the unitig strand sequences along its path.

@@ -12,6 +12,8 @@ struct SeqMeta { uint16_t id; uint32_t length; std::string filename; std::string
 std::string gfa_string(const FinalGraph& g, const std::vector<SeqMeta>& seqs, int parts = 3);
 // gfa_reader.cpp: the loader side (UnitigGraph::from_gfa_lines, unitig_graph.rs:55-174) and decompress's reconstruction
 void load_gfa(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs);
+// the same for segment numbers in any order and with holes (mapped to 1..n in file order; *numbers: the table), with the P lines' CL:i tags
+void load_gfa_any_numbers(const char* text, size_t len, FinalGraph* g, std::vector<SeqMeta>* seqs, std::vector<uint64_t>* numbers, std::vector<uint32_t>* cluster_tags);
 void decompress_sequence(const FinalGraph& g, size_t seq_index, char* out);      // out: LN bytes
 std::vector<std::string> gfa_chunks(const FinalGraph& g, const std::vector<SeqMeta>& seqs, int threads);
 // The same text for a graph whose segments carry explicit numbers and types (a graph after merge_linear_paths): the S lines print `number`

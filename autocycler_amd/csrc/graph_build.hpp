@@ -17,6 +17,7 @@
 #include "components_host.hpp"
 #include "merge_host.hpp"
 #include "subset_host.hpp"
+#include "trim_apply_host.hpp"
 #include "finish_host.hpp"
 #include "apply_host.hpp"
 #include "clean_host.hpp"
@@ -246,6 +247,14 @@ struct MergedPathsInput {
     const SubsetPlan* plan = nullptr; size_t kept_first = 0, kept_count = 0; const MergeResult* merge = nullptr;
 };
 void merged_paths_device(const MergedPathsInput& in, MergedPathsResult* out);
+// trim's edit (kernels_trim_apply.inc): the slices of tp (trim_apply_choose's) are uploaded from the caller's paths and checked against their
+// new lengths, trim_apply_exclude runs on the host in the middle, and the subset stages run with one cluster on the entries that are on the
+// device already.  Fills tp's exclusion, the plan and `out` as subset_prepare + subsets_device would.  At least one entry in the slices.
+struct TrimApplyInput {
+    uint32_t n_unitigs = 0; const Link* links = nullptr; uint64_t n_links = 0; const uint32_t* unitig_len = nullptr; const uint8_t* alive = nullptr;
+    const int32_t* path = nullptr; const uint64_t* path_off = nullptr; double mad = 0;
+};
+void trim_apply_device(const TrimApplyInput& in, TrimApplyPlan* tp, SubsetPlan* plan, SubsetResult* out);
 // A finished graph (kernels_finish.inc): a merge plan applied to the arrays it was made from — the S-line order (renumbered or not), the
 // gathered sequences, the L lines in get_links_for_gfa order and the relabelled path entries.  unitigs_after: finish_check_inputs'.
 struct FinishInput {

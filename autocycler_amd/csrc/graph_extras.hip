@@ -3,7 +3,8 @@
 // cluster's UPGMA merge loop (kernels_cluster.inc) and the QC of its clusters (kernels_cluster_qc.inc); connected components and topology
 // (kernels_components.inc); the linear-path merge plan (kernels_merge.inc); sequence subsets and the paths over merged unitigs (kernels_subset.inc);
 // the finished graph after a merge: order, renumbering, L lines (kernels_finish.inc); resolve's apply_bridges with its removals (kernels_apply.inc);
-// clean's removal, duplication and low-depth rounds (kernels_clean.inc).
+// clean's removal, duplication and low-depth rounds (kernels_clean.inc); trim's slices, length check and exclusion feeding the subset stages
+// (kernels_trim_apply.inc).
 #include "graph_impl.hpp"
 
 namespace ac {
@@ -17,6 +18,7 @@ namespace ac {
 #include "kernels_components.inc" // ac_graph_components / ac_components_from_links: connected_components, circular loops, link_count, topology (f-9)
 #include "kernels_merge.inc"   // ac_graph_merge_plan / ac_merge_plan_from_links: merge_linear_paths as a plan, with its products (f-10)
 #include "kernels_subset.inc"  // ac_graph_subsets / ac_subsets_from_paths / ac_subsets_merged_paths: what each cluster of sequences keeps (f-11)
+#include "kernels_trim_apply.inc" // ac_trim_apply / ac_graph_trim_apply / ac_graph_trim: trim's slices, exclusion and clean_up_graph's subset on resident entries (f-15)
 #include "kernels_finish.inc"  // ac_merge_finish / ac_subsets_finish: the S-line order, renumber_unitigs, the L and P lines after a merge (f-12)
 #include "kernels_apply.inc"   // ac_apply_bridges / ac_graph_resolve_apply: apply_bridges, reduce_depths and the two removals of `autocycler resolve` (f-13)
 #include "kernels_clean.inc"   // ac_clean_graph / ac_graph_clean: remove, duplicate and remove_low_depth_unitigs of `autocycler clean` (f-14)

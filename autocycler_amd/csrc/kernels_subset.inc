@@ -151,22 +151,27 @@ static void subset_upload_entries(const SubsetPlan& plan, size_t first, size_t c
     }
 }
 
-void subsets_device(const SubsetInput& in, SubsetResult* out) {
-    const u32 n = in.n_unitigs, nc = in.n_clusters;
-    const u64 nl = in.n_links;
-    const SubsetPlan& plan = *in.plan;
-    const u64 ne = plan.kept_entries(), n_kept = plan.kept_seq.size();
+// what subsets_device has put on the device before its stages run: the kept sequences' entries, cluster after cluster, and the input's arrays
+struct SubsetResident { const int32_t* path; const u64* kept_off; const u32* kept_label; const u32* unitig_len; const u8* alive; const Link* links; };
+static void subset_stages(const SubsetInput& in, const SubsetResident& d, StepMeter& meter, SubsetResult* out);
+
+static void subset_check_sizes(u32 n, u64 ne, u64 nl) {
     if (n == 0 || n > 0x7FFFFFFEu) throw DeviceError("subsets: the number of unitigs must be between 1 and 2^31 - 2 here");
     if (ne == 0) throw DeviceError("subsets: no kept entry (internal error)");
     if (ne >= 0xFFFFFFF0ULL) throw DeviceError("subsets: more than 2^32 path entries in the kept sequences");
     if (nl >= 0xFFFFFFF0ULL) throw DeviceError("subsets: more than 2^32 links");
+}
+
+// the upload, then the stages
+void subsets_device(const SubsetInput& in, SubsetResult* out) {
+    const u32 n = in.n_unitigs;
+    const u64 nl = in.n_links;
+    const SubsetPlan& plan = *in.plan;
+    const u64 ne = plan.kept_entries(), n_kept = plan.kept_seq.size();
+    subset_check_sizes(n, ne, nl);
     Arena& arena = Arena::device();
     arena.reset();
     StepMeter meter;
-    const u32 words = (nc + 63) / 64;
-    // (the links' sort always runs over all 16 bits a label can have: two passes whatever n_clusters, so that the launches follow the entry keys' width alone)
-    const int key_bits = bit_width((u64)nc * n - 1), cluster_bits = 16;
-
     DBuf<int32_t> d_path(ne);
     DBuf<u64> d_kept_off(n_kept + 1);
     DBuf<u32> d_kept_label(n_kept), d_len(n);
@@ -178,7 +183,21 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     copy_h2d(d_len.ptr(), in.unitig_len, (u64)n * 4);
     if (in.alive) copy_h2d(d_alive.ptr(), in.alive, n);
     copy_h2d(d_links.ptr(), in.links, nl * sizeof(Link));
-    const u8* p_alive = in.alive ? d_alive.ptr() : nullptr;
+    subset_stages(in, SubsetResident{d_path.ptr(), d_kept_off.ptr(), d_kept_label.ptr(), d_len.ptr(), in.alive ? d_alive.ptr() : nullptr, d_links.ptr()}, meter, out);
+}
+
+// The stages on entries that are on the device already (in.path / in.path_off: the host's copy, read for an error's text alone).  The arena
+// session and the meter are the caller's: trim_apply_device (kernels_trim_apply.inc) runs them on the entries its own stage left there.
+static void subset_stages(const SubsetInput& in, const SubsetResident& d, StepMeter& meter, SubsetResult* out) {
+    const u32 n = in.n_unitigs, nc = in.n_clusters;
+    const u64 nl = in.n_links;
+    const SubsetPlan& plan = *in.plan;
+    const u64 ne = plan.kept_entries(), n_kept = plan.kept_seq.size();
+    subset_check_sizes(n, ne, nl);
+    const u32 words = (nc + 63) / 64;
+    // (the links' sort always runs over all 16 bits a label can have: two passes whatever n_clusters, so that the launches follow the entry keys' width alone)
+    const int key_bits = bit_width((u64)nc * n - 1), cluster_bits = 16;
+    const u8* p_alive = d.alive;
 
     DBuf<u64> d_key(ne), d_pair_key(ne), d_len64(ne + 1), d_len_prefix(ne + 1), d_bits((u64)n * words), d_link_kept(nl + 1), d_link_kept_off(nl + 1), d_first_bad(3);
     DBuf<u32> d_val(ne), d_head(ne), d_rank(ne), d_pair_start(ne + 1), d_unit(ne), d_count(ne);
@@ -190,15 +209,15 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     sort_keys.prepare(ne, key_bits);
 
     meter.begin();
-    launch(ne, SubsetKeyFunctor{d_path.ptr(), d_kept_off.ptr(), d_kept_label.ptr(), n_kept, n, p_alive, d_key.ptr(), d_val.ptr(), d_first_bad.ptr()});
+    launch(ne, SubsetKeyFunctor{d.path, d.kept_off, d.kept_label, n_kept, n, p_alive, d_key.ptr(), d_val.ptr(), d_first_bad.ptr()});
     sort_pairs_u64_u32(d_key, d_val, ne, key_bits, 0, 0, &sort_keys);
     launch(ne, SubsetHeadFunctor{d_key.ptr(), d_head.ptr()});
     exclusive_scan_u32(d_head.ptr(), d_rank.ptr(), ne);
     launch(ne, SubsetCompactFunctor{d_key.ptr(), d_head.ptr(), d_rank.ptr(), ne, d_pair_key.ptr(), d_pair_start.ptr(), d_counts.ptr()});
-    launch(ne, SubsetPairFunctor{d_counts.ptr(), d_pair_key.ptr(), d_pair_start.ptr(), n, nc, words, d_len.ptr(), d_unit.ptr(), d_count.ptr(), d_len64.ptr(), d_bits.ptr()});
+    launch(ne, SubsetPairFunctor{d_counts.ptr(), d_pair_key.ptr(), d_pair_start.ptr(), n, nc, words, d.unitig_len, d_unit.ptr(), d_count.ptr(), d_len64.ptr(), d_bits.ptr()});
     exclusive_scan_u64(d_len64.ptr(), d_len_prefix.ptr(), ne + 1);
     if (nl) {
-        launch(nl, SubsetLinkCountFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept.ptr(), d_first_bad.ptr()});
+        launch(nl, SubsetLinkCountFunctor{d.links, n, words, d_bits.ptr(), d_link_kept.ptr(), d_first_bad.ptr()});
         exclusive_scan_u64(d_link_kept.ptr(), d_link_kept_off.ptr(), nl + 1);
     }
     meter.end();
@@ -225,9 +244,9 @@ void subsets_device(const SubsetInput& in, SubsetResult* out) {
     DBuf<Link> d_links_out(n_out);
     meter.begin();
     if (n_out) {
-        launch(nl, SubsetLinkKeyFunctor{d_links.ptr(), n, words, d_bits.ptr(), d_link_kept_off.ptr(), n_out, d_link_key.ptr(), d_link_val.ptr()});
+        launch(nl, SubsetLinkKeyFunctor{d.links, n, words, d_bits.ptr(), d_link_kept_off.ptr(), n_out, d_link_key.ptr(), d_link_val.ptr()});
         sort_pairs_u64_u32(d_link_key, d_link_val, n_out, 32 + cluster_bits, 0, 32);
-        launch(n_out, SubsetLinkDecodeFunctor{d_link_key.ptr(), d_links.ptr(), nl, d_links_out.ptr()});
+        launch(n_out, SubsetLinkDecodeFunctor{d_link_key.ptr(), d.links, nl, d_links_out.ptr()});
     }
     launch((u64)nc + 1, SubsetOffsetsFunctor{d_counts.ptr(), d_pair_key.ptr(), d_len_prefix.ptr(), n, d_link_key.ptr(), n_out, d_unit_off.ptr(), d_length_at.ptr(),
                                              d_link_off.ptr()});

@@ -392,7 +392,8 @@ int ac_pairwise_distances(const ac_graph*, int device, double* out);
  *              hairpin_start_trimmed / hairpin_end_trimmed say which of the two fired (the reference's message, :171-177).
  * status: 0 = not trimmed (the slice is the whole path), 1 = trimmed, 2 = the reference itself would have stopped on this input (the
  * assertion of trim.rs:310, or a path[start..end] that cannot be taken): reported, not guessed at; such a sequence counts as not trimmed.
- * Not done here (the caller applies the chosen slices): remove_sequence_from_graph, create_sequence_and_positions, clean_up_graph. */
+ * Not done here: remove_sequence_from_graph, create_sequence_and_positions, exclude_outliers_in_length, clean_up_graph — ac_graph_trim_apply /
+ * ac_trim_apply take this table and do them; ac_graph_trim and ac_trim_gfa run both halves in one call. */
 typedef struct { uint32_t status, begin, end, trimmed_length; } ac_trim_slice;
 typedef struct { ac_trim_slice start_end, hairpin; uint32_t hairpin_start_trimmed, hairpin_end_trimmed; } ac_trim_result;
 typedef struct {
@@ -891,6 +892,80 @@ int ac_clean_gfa(const char* gfa_text, uint64_t len, const char* remove, const c
 /* The whole command: in_gfa must exist; the cleaned graph is written to out_gfa.  "<in_gfa> does not contain tig N" names the file. */
 int ac_clean(const char* in_gfa, const char* out_gfa, const char* remove, const char* duplicate, int has_min_depth, double min_depth, int device);
 
+/* `autocycler trim` after the alignments, through to 2_trimmed.gfa and 2_trimmed.yaml (trim.rs:47-51): choose_trim_type (:189-226),
+ * create_sequence_and_positions' length check (unitig_graph.rs:173), exclude_outliers_in_length (:229-257) and clean_up_graph (:260-269).
+ * The slices' entries go to the device once: every entry is checked and its slice summed there (64-bit sums), the host computes median, MAD
+ * and the allowed range (f64::round half away from zero, `as usize` saturating), the kept sequences' entries are compacted on the device when
+ * somebody was excluded, and the sequence-subset stages run with one cluster on the entries that are there already.  Additions of ABI
+ * generation 13, found by name; AC_ABI_VERSION stays 13.  Read-only: the result is a new object.
+ *   chosen: AC_TRIM_CHOOSE_AUTO = choose_trim_type's rule over `results` (status 1 counts, status 2 counts as not trimmed; start-end wins a
+ *           tie; nothing is trimmed when both counts are 0), or one kind forced, or none.
+ *   A sequence whose result of the chosen kind has status 1 gets path[begin:end] and trimmed_length; every other keeps path and length.
+ *   mad: 0 excludes nobody; mad < 0 is an error.  A sequence is kept iff min <= length <= max; the kept ones keep their order.
+ * Errors (return 1, ac_last_error), never aborts: a slice whose unitig lengths do not add up to its new length (names the sequence),
+ * begin > end, end beyond the path, an entry that names no unitig or a dead one (the subsets' texts), a KEPT sequence with an empty slice
+ * (the reference asserts in find_starting_unitig, unitig_graph.rs:423), more than 32767 sequences, null pointers.  Everyone excluded is no
+ * error: the object's one cluster is empty, its text is the H line alone and no further kernel is launched. */
+typedef struct ac_trimmed ac_trimmed;
+#define AC_TRIM_CHOOSE_AUTO 0
+#define AC_TRIM_CHOOSE_NONE 1
+#define AC_TRIM_CHOOSE_START_END 2
+#define AC_TRIM_CHOOSE_HAIRPIN 3
+typedef struct {
+    uint32_t begin, end;        /* the slice of the sequence's path that stays */
+    uint64_t length;            /* its new length in bases */
+    uint32_t trimmed, excluded; /* 0 / 1 */
+} ac_trimmed_record;
+typedef struct {
+    uint32_t size;              /* the library's sizeof(ac_trimmed_summary) */
+    uint32_t chosen;            /* 0 = none, 1 = start-end, 2 = hairpin (ac_trim_summary.chosen's values) */
+    uint32_t c_se, c_hp;        /* results with status 1 per kind */
+    uint32_t sequences, trimmed, excluded, rejected;   /* in; given a slice; outside the range; with a status-2 result of either kind */
+    uint32_t unitigs_in, unitigs_alive;                /* of the input; visited by a kept slice */
+    uint32_t launches, read_backs;                     /* of the edit: the slice stage and the subset stages */
+    uint64_t median, mad;       /* median_isize / mad_isize of the new lengths of all sequences */
+    uint64_t min_length, max_length;                   /* the allowed range; 0 and 2^64 - 1 when mad == 0 */
+    uint64_t entries_kept, links;                      /* path entries of the kept slices; links between alive unitigs */
+    double seconds_device;      /* the edit's kernels, by device events */
+    uint32_t align_launches, reserved;                 /* ac_graph_trim / ac_trim_gfa: the alignment, as ac_trim_summary reports it (else 0) */
+    uint64_t align_cells;
+    double align_seconds_device;
+} ac_trimmed_summary;
+/* On the caller's arrays: links / unitig_len / alive as for ac_subsets_from_paths, path_entries / path_off / seq_length per sequence, results =
+ * ac_trim_path_slices' table (may be NULL with AC_TRIM_CHOOSE_NONE).  The arrays except `results` are borrowed until ac_trimmed_free. */
+int ac_trim_apply(uint32_t n_unitigs, const ac_link* links, uint64_t n_links, const uint32_t* unitig_len, const uint8_t* alive /* or NULL */,
+        const uint8_t* type /* AC_UNITIG_*, or NULL = Other */, const int32_t* path_entries, const uint64_t* path_off, const uint32_t* seq_length,
+        uint32_t n_seqs, const ac_trim_result* results, uint32_t chosen, double mad, int device, ac_trimmed** out);
+/* The same on a handle (which must outlive the object); results = ac_trim_paths' table. */
+int ac_graph_trim_apply(const ac_graph*, const ac_trim_result* results, uint32_t chosen, double mad, int device, ac_trimmed** out);
+/* ac_trim_paths' computation followed by the edit (chosen = auto).  min_identity outside [0, 1]: "--min_identity must be between 0.0 and 1
+ * (inclusive)"; mad < 0: "--mad cannot be less than 0" (trim.rs:60-65).  max_unitigs = 0 disables trimming, not the exclusion. */
+int ac_graph_trim(const ac_graph*, double min_identity, uint32_t max_unitigs, double mad, int device, ac_trimmed** out);
+int ac_trimmed_records(const ac_trimmed*, const ac_trimmed_record** records, uint32_t* n_seqs);
+size_t ac_trimmed_summary_get_sized(const ac_trimmed*, ac_trimmed_summary* out, size_t out_size);
+void ac_trimmed_free(ac_trimmed*);
+/* The trimmed graph before the merge, as a borrowed one-cluster ac_subsets (do not free it; it dies with the object): every ac_subsets_*
+ * accessor and composed entry serves it as it stands, cluster = 1.  Its sequences are the input's, the excluded ones with label 0; its
+ * paths are the slices. */
+const ac_subsets* ac_trimmed_subsets(const ac_trimmed*);
+/* merge_linear_paths with the kept paths' ends fixed, the paths over the merged unitigs and renumber_unitigs in one call: the finished graph
+ * (ac_finished_free).  seq_bytes / seq_begin: the unitigs' bases for the S lines, NULL, NULL on a handle-made object (the handle's are
+ * used) or for a finish without sequences.  ac_finished_gfa_string with the kept sequences' ids, NEW lengths, file names and headers prints
+ * 2_trimmed.gfa; ac_finished_to_graph gives the handle `resolve` starts from. */
+int ac_trimmed_finish(const ac_trimmed*, const uint8_t* seq_bytes, const uint64_t* seq_begin, int device, ac_finished** out);
+/* 2_trimmed.yaml: TrimmedClusterMetrics (metrics.rs:213-230) in serde_yaml 0.9 block style.  *out is malloc'ed (ac_string_free). */
+int ac_trimmed_yaml_string(const ac_trimmed*, char** out, uint64_t* len /* may be NULL */);
+/* trim.rs:43-51 from text to texts.  Reads GFAs as `cluster` writes them (save_cluster_gfa, cluster.rs:794-806): segment numbers in any
+ * order and with holes, mapped to 1..n in file order (the output does not depend on them: trim compares entries for equality and renumbers
+ * at its end); the P lines' CL:i tags and the S lines' colours are kept.  *gfa and *yaml are malloc'ed (ac_string_free); summary may be NULL. */
+int ac_trim_gfa(const char* gfa_text, uint64_t len, double min_identity, uint32_t max_unitigs, double mad, int device, char** gfa, uint64_t* gfa_len,
+        char** yaml, ac_trimmed_summary* summary /* its size field set by the caller */);
+/* The whole command: <cluster_dir>/1_untrimmed.gfa -> 2_trimmed.gfa and 2_trimmed.yaml, each written to a temporary file and renamed. */
+int ac_trim_dir(const char* cluster_dir, double min_identity, uint32_t max_unitigs, double mad, int device);
+/* `autocycler resolve` as a command (resolve.rs:41-67 without --verbose): <cluster_dir>/2_trimmed.gfa -> 3_bridged.gfa, 4_merged.gfa and
+ * 5_final.gfa through ac_resolve_graphs. */
+int ac_resolve_dir(const char* cluster_dir, int device);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -1202,7 +1277,9 @@ const char* ac_version(void);
  *      ac_applied_finish, ac_applied_gfa_string, ac_resolve_graphs with ac_applied_summary and the AC_APPLY_* values; then, likewise:
  *      ac_clean_graph, ac_graph_clean, ac_cleaned_unitigs, ac_cleaned_links, ac_cleaned_summary_get_sized, ac_cleaned_free,
  *      ac_cleaned_merge_plan, ac_cleaned_finish, ac_cleaned_gfa_string, ac_parse_tig_numbers, ac_gfa_segment_types, ac_clean_gfa, ac_clean
- *      with ac_cleaned_summary and the AC_CLEAN_* values. */
+ *      with ac_cleaned_summary and the AC_CLEAN_* values; then, likewise: ac_trim_apply, ac_graph_trim_apply, ac_graph_trim,
+ *      ac_trimmed_records, ac_trimmed_summary_get_sized, ac_trimmed_free, ac_trimmed_subsets, ac_trimmed_finish, ac_trimmed_yaml_string,
+ *      ac_trim_gfa, ac_trim_dir, ac_resolve_dir with ac_trimmed_record, ac_trimmed_summary and the AC_TRIM_CHOOSE_* values. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
