@@ -187,6 +187,26 @@ class TrimmedSummary(C.Structure):      # ac_trimmed_summary
         return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("size", "reserved")}
 
 
+class CombinedCluster(C.Structure):      # ac_combined_cluster
+    _fields_ = [("input_index", C.c_uint32), ("unitigs", C.c_uint32), ("length", C.c_uint64), ("links", C.c_uint64), ("offset", C.c_uint64), ("max_number", C.c_uint32),
+                ("topology", C.c_uint32), ("has_read_depth", C.c_uint32), ("reserved", C.c_uint32), ("read_depth", C.c_double)]
+
+
+class CombinedUnitig(C.Structure):      # ac_combined_unitig
+    _fields_ = [("graph", C.c_uint32), ("index", C.c_uint32), ("number", C.c_uint32), ("length", C.c_uint32), ("depth", C.c_double), ("read_depth", C.c_double),
+                ("has_read_depth", C.c_uint8), ("flags", C.c_uint8), ("type", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class CombinedSummary(C.Structure):      # ac_combined_summary
+    _fields_ = [("size", C.c_uint32), ("graphs", C.c_uint32), ("bases", C.c_uint64), ("unitigs", C.c_uint64), ("links", C.c_uint64), ("fully_resolved", C.c_uint32),
+                ("with_reads", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "size"}
+        d["fully_resolved"], d["with_reads"] = bool(d["fully_resolved"]), bool(d["with_reads"])
+        return d
+
+
 class ClusterNode(C.Structure):      # ac_cluster_node
     _fields_ = [("id", C.c_uint16), ("left", C.c_int32), ("right", C.c_int32), ("distance", C.c_double)]
 
@@ -245,7 +265,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
 EXPORTS = ["ac_compress_build", "ac_compress_build_multi", "ac_multi_info_get", "ac_compress_build_device", "ac_pack_text", "ac_text_size", "ac_layout_text", "ac_kmer_count",
            "ac_stats_pre", "ac_stats_post", "ac_unitig_count", "ac_unitig", "ac_unitigs_bulk", "ac_paths_bulk", "ac_unitig_positions", "ac_links",
            "ac_path", "ac_timings_get", "ac_timings_get_sized", "ac_free", "ac_gfa_string", "ac_string_free", "ac_last_error",
-           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_clean_graph", "ac_graph_clean", "ac_cleaned_unitigs", "ac_cleaned_links", "ac_cleaned_summary_get_sized", "ac_cleaned_free", "ac_cleaned_merge_plan", "ac_cleaned_finish", "ac_cleaned_gfa_string", "ac_parse_tig_numbers", "ac_gfa_segment_types", "ac_clean_gfa", "ac_clean", "ac_trim_apply", "ac_graph_trim_apply", "ac_graph_trim", "ac_trimmed_records", "ac_trimmed_summary_get_sized", "ac_trimmed_free", "ac_trimmed_subsets", "ac_trimmed_finish", "ac_trimmed_yaml_string", "ac_trim_gfa", "ac_trim_dir", "ac_resolve_dir", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
+           "ac_device_count", "ac_max_kmer", "ac_version", "ac_abi_version", "ac_set_host_side_device", "ac_source_hash", "ac_set_stage_timing", "ac_random_access_ceilings", "ac_random_access_ceilings_at", "ac_release_memory", "ac_end_repair_device", "ac_pairwise_distances", "ac_trim_paths", "ac_trim_path_slices", "ac_overlap_alignment", "ac_trim_max_unitigs", "ac_resolve_bridges", "ac_resolve_bridge_paths", "ac_path_distances", "ac_resolve_anchors", "ac_resolve_bridge_records", "ac_resolve_best_paths", "ac_resolve_distinct_paths", "ac_resolve_summary_get_sized", "ac_resolve_max_path", "ac_resolve_free", "ac_graph_components", "ac_components_from_links", "ac_components_records", "ac_components_of_unitig", "ac_components_members", "ac_components_unitig_flags", "ac_components_summary_get_sized", "ac_topology_name", "ac_components_free", "ac_graph_merge_plan", "ac_merge_plan_from_links", "ac_merge_chains", "ac_merge_members", "ac_merge_chain_of_unitig", "ac_merge_fixed_flags", "ac_merge_sequences", "ac_merge_links", "ac_merge_summary_get_sized", "ac_merge_free", "ac_graph_subsets", "ac_subsets_from_paths", "ac_subsets_records", "ac_subsets_unitigs", "ac_subsets_links", "ac_subsets_seqs", "ac_subsets_path_ends", "ac_subsets_dense", "ac_subsets_summary_get_sized", "ac_subsets_free", "ac_subsets_components", "ac_subsets_merge_plan", "ac_subsets_merged_paths", "ac_merged_paths_get", "ac_merged_paths_summary_get_sized", "ac_merged_paths_free", "ac_merge_finish", "ac_subsets_finish", "ac_finished_unitigs", "ac_finished_sequences", "ac_finished_new_of_old", "ac_finished_links", "ac_finished_paths", "ac_finished_summary_get_sized", "ac_finished_free", "ac_finished_gfa_string", "ac_finished_to_graph", "ac_apply_bridges", "ac_graph_resolve_apply", "ac_applied_unitigs", "ac_applied_bridge_of", "ac_applied_links", "ac_applied_bridge_sequences", "ac_applied_summary_get_sized", "ac_applied_free", "ac_applied_merge_plan", "ac_applied_finish", "ac_applied_gfa_string", "ac_resolve_graphs", "ac_clean_graph", "ac_graph_clean", "ac_cleaned_unitigs", "ac_cleaned_links", "ac_cleaned_summary_get_sized", "ac_cleaned_free", "ac_cleaned_merge_plan", "ac_cleaned_finish", "ac_cleaned_gfa_string", "ac_parse_tig_numbers", "ac_gfa_segment_types", "ac_clean_gfa", "ac_clean", "ac_trim_apply", "ac_graph_trim_apply", "ac_graph_trim", "ac_trimmed_records", "ac_trimmed_summary_get_sized", "ac_trimmed_free", "ac_trimmed_subsets", "ac_trimmed_finish", "ac_trimmed_yaml_string", "ac_trim_gfa", "ac_trim_dir", "ac_resolve_dir", "ac_combine_graphs", "ac_combine_handles", "ac_combined_clusters", "ac_combined_unitigs", "ac_combined_links", "ac_combined_summary_get_sized", "ac_combined_free", "ac_combined_gfa_string", "ac_combined_fasta_string", "ac_combined_yaml_string", "ac_combined_depth_lines", "ac_combine_gfas", "ac_combine", "ac_gfa2fasta_string", "ac_gfa2fasta", "ac_cluster_tree_build", "ac_cluster_tree_from_distances", "ac_cluster_tree_from_nodes", "ac_cluster_nodes", "ac_cluster_merges", "ac_cluster_summary_get_sized", "ac_cluster_free", "ac_cluster_max_seqs", "ac_cluster_cut", "ac_cluster_assign", "ac_cluster_containment", "ac_cluster_newick", "ac_cluster_generate", "ac_cluster_qc_nodes", "ac_cluster_qc_clusters", "ac_cluster_qc_assignment", "ac_cluster_qc_records", "ac_cluster_qc_metrics", "ac_cluster_qc_trace", "ac_cluster_qc_summary_get_sized", "ac_cluster_qc_free", "ac_cluster_min_assemblies", "ac_cluster_seq_inputs", "ac_depth_begin", "ac_depth_begin_handles", "ac_depth_add_reads", "ac_depth_add_fastq", "ac_depth_totals_get", "ac_depth_kmer_counts", "ac_depth_finish", "ac_depth_free", "ac_selftest_primitives", "ac_selftest_scan", "ac_selftest_radix", "ac_selftest_segments", "ac_selftest_sort_cmp", "ac_selftest_scan_pool", "ac_selftest_wave", "ac_selftest_fills", "ac_selftest_fill_order", "ac_selftest_readback", "ac_selftest_scalar_chain", "ac_selftest_arena", "ac_selftest_launch", "ac_selftest_atomics", "ac_selftest_side_order", "ac_selftest_event_ring", "ac_verify_graph", "ac_verify_graph_device", "ac_graph_from_gfa", "ac_graph_kmer_size", "ac_graph_seq_info", "ac_decompress_seq", "ac_decompress_device", "ac_decompress",
            "ac_shard_begin", "ac_shard_fragment_sizes", "ac_shard_fragments_export", "ac_shard_build_union", "ac_shard_fragment_packed_words", "ac_shard_fragments_export_packed", "ac_shard_build_union_packed",
            "ac_shard_unitig_count", "ac_shard_table_capacity", "ac_shard_bitmap_words", "ac_shard_bitmap_export", "ac_shard_build_novel", "ac_shard_sib_words", "ac_shard_sib_export", "ac_shard_degrees",
            "ac_shard_degree_bytes", "ac_multi_info_get_sized", "ac_shard_links_export", "ac_shard_links_import",
@@ -448,6 +468,22 @@ def load_library(path=None):
                                 C.POINTER(TrimmedSummary)]
     lib.ac_trim_dir.argtypes = [C.c_char_p, C.c_double, C.c_uint32, C.c_double, C.c_int]
     lib.ac_resolve_dir.argtypes = [C.c_char_p, C.c_int]
+    lib.ac_combine_graphs.argtypes = [C.c_uint32] + [C.c_void_p] * 11 + [C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_combine_handles.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_combined_clusters.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CombinedCluster)), C.POINTER(C.c_uint32)]
+    lib.ac_combined_unitigs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CombinedUnitig)), C.POINTER(C.c_uint64)]
+    lib.ac_combined_links.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Link)), C.POINTER(C.c_uint64)]
+    lib.ac_combined_summary_get_sized.restype = C.c_size_t
+    lib.ac_combined_summary_get_sized.argtypes = [C.c_void_p, C.POINTER(CombinedSummary), C.c_size_t]
+    lib.ac_combined_free.argtypes = [C.c_void_p]
+    lib.ac_combined_free.restype = None
+    for f in (lib.ac_combined_gfa_string, lib.ac_combined_fasta_string, lib.ac_combined_yaml_string, lib.ac_combined_depth_lines):
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    lib.ac_combine_gfas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(CombinedSummary)]
+    lib.ac_combine.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ac_gfa2fasta_string.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.ac_gfa2fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
     lib.ac_resolve_graphs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
     lib.ac_cluster_tree_from_nodes.argtypes = [C.POINTER(ClusterNode), C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ac_cluster_nodes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ClusterNode)), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
@@ -1422,6 +1458,207 @@ def resolve_dir(cluster_dir, device=0, lib_path=None):
     """ac_resolve_dir: <cluster_dir>/2_trimmed.gfa -> 3_bridged.gfa, 4_merged.gfa, 5_final.gfa"""
     lib = load_library(lib_path)
     _check(lib, lib.ac_resolve_dir(str(cluster_dir).encode(), device))
+
+
+TOPOLOGY_NAMES = ("empty", "fragmented", "linear-open-open", "circular", "linear-hairpin-hairpin", "linear-open-hairpin", "other")      # AC_TOPOLOGY_*
+
+
+class Combined:
+    """Owning handle of an ac_combined: the clusters' graphs as `autocycler combine` (combine.rs:144-224) puts them together.  The records are
+    copied out on construction; the handle stays for gfa(), fasta(), yaml() and depth_lines() until close().
+    clusters   structured array, one per graph in output order: input_index, unitigs, length, links, offset, max_number, topology (an index into
+               TOPOLOGY_NAMES), has_read_depth, read_depth
+    unitigs    structured array, one per unitig in output order: graph, index, number (printed), length, depth (printed), read_depth,
+               has_read_depth, flags (as Components.flags), type
+    links      (m, 2) int32 of printed numbers, graph after graph, in get_links_for_gfa order
+    summary    dict: graphs, bases, unitigs, links, fully_resolved, with_reads, launches, read_backs, seconds_device"""
+
+    def __init__(self, lib, h):
+        import numpy as np
+        self._lib, self._h = lib, h
+        cp, cn = C.POINTER(CombinedCluster)(), C.c_uint32()
+        _check(lib, lib.ac_combined_clusters(h, C.byref(cp), C.byref(cn)))
+        self.clusters = np.frombuffer(C.string_at(cp, cn.value * C.sizeof(CombinedCluster)), dtype=np.dtype(CombinedCluster)).copy()
+        up, un = C.POINTER(CombinedUnitig)(), C.c_uint64()
+        _check(lib, lib.ac_combined_unitigs(h, C.byref(up), C.byref(un)))
+        self.unitigs = np.frombuffer(C.string_at(up, un.value * C.sizeof(CombinedUnitig)) if un.value else b"", dtype=np.dtype(CombinedUnitig)).copy()
+        kp, kn = C.POINTER(Link)(), C.c_uint64()
+        _check(lib, lib.ac_combined_links(h, C.byref(kp), C.byref(kn)))
+        self.links = _take(kp, 2 * kn.value, "<i4").reshape(-1, 2)
+        sm = CombinedSummary()
+        assert lib.ac_combined_summary_get_sized(h, C.byref(sm), C.sizeof(CombinedSummary)) == C.sizeof(CombinedSummary) == sm.size
+        self.summary = sm.as_dict()
+
+    def close(self):
+        if self._h:
+            self._lib.ac_combined_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _text(self, f):
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, f(self._h, C.byref(out), C.byref(n)))
+        text = C.string_at(out.value, n.value)
+        self._lib.ac_string_free(out)
+        return text
+
+    def gfa(self):
+        """ac_combined_gfa_string: consensus_assembly.gfa (bytes)"""
+        return self._text(self._lib.ac_combined_gfa_string)
+
+    def fasta(self):
+        """ac_combined_fasta_string: consensus_assembly.fasta (bytes)"""
+        return self._text(self._lib.ac_combined_fasta_string)
+
+    def yaml(self):
+        """ac_combined_yaml_string: consensus_assembly.yaml (bytes)"""
+        return self._text(self._lib.ac_combined_yaml_string)
+
+    def depth_lines(self):
+        """ac_combined_depth_lines: what print_read_depths writes on stderr (bytes; empty without reads)"""
+        return self._text(self._lib.ac_combined_depth_lines)
+
+
+def _read_depth_lists(read_depths, sizes):
+    """read depths as the entries take them.  read_depths: None, a ReadDepth (its depths(g) of every graph), or one sequence per graph of floats
+    with None where there is no depth (what ReadDepth.depths returns).  -> (depth arrays, has arrays), one pair per graph, or (None, None)"""
+    import numpy as np
+    if read_depths is None:
+        return None, None
+    if isinstance(read_depths, ReadDepth):
+        read_depths = [read_depths.depths(g) for g in range(len(sizes))]
+    if len(read_depths) != len(sizes):
+        raise AutocyclerError(f"read_depths: one entry per graph expected ({len(sizes)}), got {len(read_depths)}")
+    rd, has = [], []
+    for g, (v, n) in enumerate(zip(read_depths, sizes)):
+        v = list(v)
+        if len(v) != n:
+            raise AutocyclerError(f"read_depths[{g}]: one entry per unitig expected ({n}), got {len(v)}")
+        rd.append(np.array([0.0 if x is None else float(x) for x in v] + [0.0], dtype=np.float64))
+        has.append(np.array([0 if x is None else 1 for x in v] + [0], dtype=np.uint8))
+    return rd, has
+
+
+def _pointer_list(arrays):
+    return (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+
+
+def combine_graphs(graphs, read_depths=None, device=0, lib_path=None):
+    """ac_combine_graphs: `autocycler combine` on plain arrays.  graphs: one dict per graph with
+    number (per unitig), len, links ((a, b) pairs of signed 1-based file-order indices within the graph, in L-line order) and optionally depth,
+    type, seqs (one bytes object per unitig: needed for gfa() and fasta() only).  read_depths: see _read_depth_lists.  A Combined."""
+    import numpy as np
+    lib = load_library(lib_path)
+    graphs = list(graphs)
+    sizes = [len(g["number"]) for g in graphs]
+    for g, n in zip(graphs, sizes):
+        for key in ("len", "depth", "type"):
+            if g.get(key) is not None and len(g[key]) != n:
+                raise AutocyclerError(f"{key}: one entry per unitig expected ({n}), got {len(g[key])}")
+    uoff = np.zeros(len(graphs) + 1, dtype=np.uint64); loff = np.zeros(len(graphs) + 1, dtype=np.uint64)
+
+    def cat(key, dtype):
+        parts = [np.asarray(g[key], dtype=dtype).reshape(-1) if g.get(key) is not None else np.zeros(n, dtype=dtype) for g, n in zip(graphs, sizes)]
+        return np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, dtype=dtype)]))
+    number, ln, depth, ty = cat("number", np.uint32), cat("len", np.uint32), cat("depth", np.float64), cat("type", np.uint8)
+    link_arrays = [np.asarray(g.get("links", []), dtype=np.int32).reshape(-1, 2) for g in graphs]
+    links = np.ascontiguousarray(np.concatenate(link_arrays + [np.zeros((1, 2), dtype=np.int32)]))
+    if graphs:
+        uoff[1:] = np.cumsum(sizes); loff[1:] = np.cumsum([a.shape[0] for a in link_arrays])
+    rd, has = _read_depth_lists(read_depths, sizes)
+    rd_all = np.ascontiguousarray(np.concatenate([a[:-1] for a in rd] + [np.zeros(1)])) if rd is not None else None
+    has_all = np.ascontiguousarray(np.concatenate([a[:-1] for a in has] + [np.zeros(1, dtype=np.uint8)])) if has is not None else None
+    sb = sg = None
+    if graphs and all(g.get("seqs") is not None for g in graphs):
+        seqs = [bytes(x) for g in graphs for x in g["seqs"]]
+        if len(seqs) != sum(sizes):
+            raise AutocyclerError("seqs: one entry per unitig expected")
+        sg = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        sg[1:] = np.cumsum([len(x) for x in seqs])
+        sb = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    h = C.c_void_p()
+    _check(lib, lib.ac_combine_graphs(len(graphs), ptr(uoff), ptr(loff), ptr(number), ptr(ln), ptr(depth), ptr(ty), ptr(links), ptr(rd_all), ptr(has_all), ptr(sb), ptr(sg),
+                                      device, C.byref(h)))
+    return Combined(lib, h)
+
+
+def combine_handles(graphs, types=None, read_depths=None, device=0, lib_path=None):
+    """ac_combine_handles: the same on Graph handles (graph_from_gfa of each 5_final.gfa).  types: one uint8 array per graph (gfa_segment_types of
+    its text) or None = Other.  A Combined."""
+    import numpy as np
+    lib = load_library(lib_path)
+    graphs = list(graphs)
+    sizes = [g.unitig_count for g in graphs]
+    hs = (C.c_void_p * max(len(graphs), 1))(*[g._h for g in graphs])
+    ty = None
+    if types is not None:
+        ty = [np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.uint8), np.zeros(1, dtype=np.uint8)])) for t in types]
+        if [len(t) - 1 for t in ty] != sizes:
+            raise AutocyclerError("types: one array per graph with one entry per unitig expected")
+    rd, has = _read_depth_lists(read_depths, sizes)
+    h = C.c_void_p()
+    _check(lib, lib.ac_combine_handles(hs, len(graphs), _pointer_list(ty) if ty is not None else None, _pointer_list(rd) if rd is not None else None,
+                                       _pointer_list(has) if has is not None else None, device, C.byref(h)))
+    return Combined(lib, h)
+
+
+def combine_gfas(texts, read_depths=None, device=0, lib_path=None):
+    """ac_combine_gfas: from the texts of the clusters' GFAs -> (consensus_assembly.gfa, .fasta, .yaml as bytes, summary dict).  read_depths: see
+    _read_depth_lists (per graph in S-line order)."""
+    lib = load_library(lib_path)
+    bs = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    tp = (C.c_char_p * max(len(bs), 1))(*bs)
+    tn = (C.c_uint64 * max(len(bs), 1))(*[len(b) for b in bs])
+    sizes = [sum(1 for line in b.split(b"\n") if line.split(b"\t")[0] == b"S") for b in bs]
+    rd, has = _read_depth_lists(read_depths, sizes)
+    gfa, fasta, yaml = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    gn, fn, yn = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    sm = CombinedSummary()
+    sm.size = C.sizeof(CombinedSummary)
+    _check(lib, lib.ac_combine_gfas(tp, tn, len(bs), _pointer_list(rd) if rd is not None else None, _pointer_list(has) if has is not None else None, device,
+                                    C.byref(gfa), C.byref(gn), C.byref(fasta), C.byref(fn), C.byref(yaml), C.byref(yn), C.byref(sm)))
+    out = C.string_at(gfa.value, gn.value), C.string_at(fasta.value, fn.value), C.string_at(yaml.value, yn.value)
+    for p in (gfa, fasta, yaml):
+        lib.ac_string_free(p)
+    return out[0], out[1], out[2], sm.as_dict()
+
+
+def combine_dir(autocycler_dir, in_gfas, reads=(), depth_kmer=19, device=0, lib_path=None):
+    """ac_combine: the whole command -> what it would print on stderr after the work (str): the depth lines, then the verdict"""
+    lib = load_library(lib_path)
+    gs = [os.fsencode(str(p)) for p in in_gfas]
+    rs = [os.fsencode(str(p)) for p in reads]
+    report = C.c_void_p()
+    _check(lib, lib.ac_combine(os.fsencode(str(autocycler_dir)), (C.c_char_p * max(len(gs), 1))(*gs), len(gs), (C.c_char_p * max(len(rs), 1))(*rs) if rs else None, len(rs),
+                               depth_kmer, device, C.byref(report)))
+    text = C.string_at(report.value).decode()
+    lib.ac_string_free(report)
+    return text
+
+
+def gfa2fasta(gfa_text, device=0, lib_path=None):
+    """ac_gfa2fasta_string: `autocycler gfa2fasta` from a GFA text -> (FASTA as bytes, (circular, linear, other))"""
+    lib = load_library(lib_path)
+    b = gfa_text.encode() if isinstance(gfa_text, str) else gfa_text
+    out, n, counts = C.c_void_p(), C.c_uint64(), (C.c_uint64 * 3)()
+    _check(lib, lib.ac_gfa2fasta_string(b, len(b), device, C.byref(out), C.byref(n), counts))
+    text = C.string_at(out.value, n.value)
+    lib.ac_string_free(out)
+    return text, tuple(counts)
+
+
+def gfa2fasta_file(in_gfa, out_fasta, device=0, lib_path=None):
+    """ac_gfa2fasta: the command on files -> (circular, linear, other)"""
+    lib = load_library(lib_path)
+    counts = (C.c_uint64 * 3)()
+    _check(lib, lib.ac_gfa2fasta(os.fsencode(str(in_gfa)), os.fsencode(str(out_fasta)), device, counts))
+    return tuple(counts)
 
 
 class Finished:

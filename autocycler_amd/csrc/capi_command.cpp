@@ -360,4 +360,107 @@ int ac_resolve_dir(const char* cluster_dir, int device) {
     });
 }
 
+// ---- `combine` and `gfa2fasta` as commands: the text entries of capi_combine.cpp between reads and write_pieces ----
+static std::string read_input_file(const char* path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw UserError(std::string("file does not exist: ") + path);
+    return std::string(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+}
+// combine.rs:28-54
+int ac_combine(const char* autocycler_dir, const char* const* in_gfas, uint32_t n_gfas, const char* const* reads, uint32_t n_reads, uint32_t depth_kmer, int device,
+               char** report) {
+    return guarded([&] {
+        if (report) *report = nullptr;
+        if (!autocycler_dir) throw DeviceError("null pointer: autocycler_dir");
+        if (n_gfas == 0) throw DeviceError("combine: at least one graph is required");
+        if (!in_gfas || (n_reads && !reads)) throw DeviceError("null pointer: in_gfas and reads");
+        // check_settings (combine.rs:57-67)
+        for (uint32_t i = 0; i < n_gfas; i++) if (!in_gfas[i] || !fs::is_regular_file(in_gfas[i])) throw UserError(std::string("file does not exist: ") + (in_gfas[i] ? in_gfas[i] : "(null)"));
+        for (uint32_t i = 0; i < n_reads; i++) if (!reads[i] || !fs::is_regular_file(reads[i])) throw UserError(std::string("file does not exist: ") + (reads[i] ? reads[i] : "(null)"));
+        if (n_reads) {
+            if (depth_kmer < 11) throw UserError("--depth_kmer cannot be less than 11");
+            if (depth_kmer > 31) throw UserError("--depth_kmer cannot be greater than 31");
+            if (depth_kmer % 2 == 0) throw UserError("--depth_kmer must be odd");
+        }
+        std::error_code ec;
+        fs::create_directories(autocycler_dir, ec);
+        if (ec) throw UserError(std::string("failed to create directory ") + autocycler_dir + "\n" + ec.message());
+        std::vector<std::string> texts(n_gfas);
+        std::vector<const char*> text_p(n_gfas);
+        std::vector<uint64_t> text_n(n_gfas);
+        for (uint32_t i = 0; i < n_gfas; i++) { texts[i] = read_input_file(in_gfas[i]); text_p[i] = texts[i].data(); text_n[i] = texts[i].size(); }
+        // set_read_depths over all graphs together: one table
+        std::vector<std::vector<double>> rd(n_gfas);
+        std::vector<std::vector<uint8_t>> has(n_gfas);
+        std::vector<const double*> rd_p; std::vector<const uint8_t*> has_p;
+        if (n_reads) {
+            std::vector<CombineGfa> loaded(n_gfas);
+            std::vector<ac_depth_graph> dg(n_gfas);
+            for (uint32_t i = 0; i < n_gfas; i++) {
+                combine_load_gfa(text_p[i], text_n[i], &loaded[i]);
+                const CombineGfa& c = loaded[i];
+                dg[i] = ac_depth_graph{(const uint8_t*)text_p[i], c.seq_at.data(), c.len.data(), (uint32_t)c.number.size(), (const ac_link*)c.links.data(), c.links.size()};
+            }
+            ac_depth* dp = nullptr;
+            if (ac_depth_begin(depth_kmer, dg.data(), n_gfas, device, &dp) != 0) throw DeviceError(last_error());
+            struct FreeDepth { void operator()(ac_depth* p) const { ac_depth_free(p); } };
+            std::unique_ptr<ac_depth, FreeDepth> d(dp);
+            for (uint32_t i = 0; i < n_reads; i++) if (ac_depth_add_fastq(d.get(), reads[i]) != 0) throw DeviceError(last_error());
+            for (uint32_t i = 0; i < n_gfas; i++) {
+                rd[i].assign(loaded[i].number.size() + 1, 0.0); has[i].assign(loaded[i].number.size() + 1, 0);
+                if (ac_depth_finish(d.get(), i, rd[i].data(), has[i].data()) != 0) throw DeviceError(last_error());
+                rd_p.push_back(rd[i].data()); has_p.push_back(has[i].data());
+            }
+        }
+        OwnedText gfa, fasta, yaml;
+        uint64_t gfa_n = 0, fasta_n = 0, yaml_n = 0;
+        ac_combined_summary sm;
+        memset(&sm, 0, sizeof sm);
+        sm.size = (uint32_t)sizeof sm;
+        if (ac_combine_gfas(text_p.data(), text_n.data(), n_gfas, n_reads ? rd_p.data() : nullptr, n_reads ? has_p.data() : nullptr, device, &gfa.p, &gfa_n, &fasta.p, &fasta_n,
+                            &yaml.p, &yaml_n, &sm) != 0)
+            throw DeviceError(last_error());
+        const fs::path dir(autocycler_dir);
+        write_pieces((dir / "consensus_assembly.gfa").string(), {std::string(gfa.p, gfa_n)}, 1);
+        write_pieces((dir / "consensus_assembly.fasta").string(), {std::string(fasta.p, fasta_n)}, 1);
+        write_pieces((dir / "consensus_assembly.yaml").string(), {std::string(yaml.p, yaml_n)}, 1);
+        if (report) {
+            // print_read_depths (combine.rs:94-104) from the FASTA's own headers, then finished_message's verdict
+            std::string r;
+            if (n_reads) {
+                r = "Sequence depths:\n";
+                const std::string f(fasta.p, fasta_n);
+                size_t a = 0;
+                while (a < f.size()) {
+                    size_t e = f.find('\n', a);
+                    if (e == std::string::npos) e = f.size();
+                    if (f[a] == '>') {
+                        std::string h = f.substr(a + 1, e - a - 1);
+                        const size_t cut = h.find(" circular=");
+                        if (cut != std::string::npos) h.resize(cut);
+                        r += "  " + h + "\n";
+                    }
+                    a = e + 1;
+                }
+            }
+            r += sm.fully_resolved ? "Consensus assembly is fully resolved\n" : "One or more clusters failed to fully resolve\n";
+            char* p = (char*)malloc(r.size() + 1);
+            if (!p) throw DeviceError("out of memory");
+            memcpy(p, r.c_str(), r.size() + 1);
+            *report = p;
+        }
+    });
+}
+// gfa2fasta.rs:25-36
+int ac_gfa2fasta(const char* in_gfa, const char* out_fasta, int device, uint64_t* counts) {
+    return guarded([&] {
+        if (!in_gfa || !out_fasta) throw DeviceError("null pointer: in_gfa and out_fasta are required");
+        const std::string text = read_input_file(in_gfa);
+        OwnedText fasta;
+        uint64_t n = 0;
+        if (ac_gfa2fasta_string(text.data(), text.size(), device, &fasta.p, &n, counts) != 0) throw DeviceError(last_error());
+        write_pieces(out_fasta, {std::string(fasta.p, n)}, 1);
+    });
+}
+
 }  // extern "C"

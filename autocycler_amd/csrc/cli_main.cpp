@@ -123,8 +123,80 @@ static int cluster_dir_main(int argc, char** argv, bool trim) {
     return 0;
 }
 
+// `autocycler combine` (main.rs: Combine): -a/--autocycler_dir DIR  -i/--in_gfas A.gfa [B.gfa ...]  [-r/--reads R.fastq ...]  [--depth_kmer 19]  [--device 0]
+static int combine_main(int argc, char** argv) {
+    std::string dir;
+    std::vector<const char*> gfas, reads;
+    unsigned depth_kmer = 19;
+    int device = 0;
+    const char* use = "Usage: autocycler-compress combine --autocycler_dir <DIR> --in_gfas <GFA>... [--reads <FASTQ>...] [--depth_kmer 19] [--device 0]\n";
+    std::vector<const char*>* list = nullptr;      // the option whose values are being read
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto val = [&]() -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", a.c_str()); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-a" || a == "--autocycler_dir") { dir = val(); list = nullptr; }
+        else if (a == "-i" || a == "--in_gfas") { gfas.push_back(val()); list = &gfas; }
+        else if (a == "-r" || a == "--reads") { reads.push_back(val()); list = &reads; }
+        else if (a == "--depth_kmer") { depth_kmer = (unsigned)strtoul(val(), nullptr, 10); list = nullptr; }
+        else if (a == "--device") { device = atoi(val()); list = nullptr; }
+        else if (list && !a.empty() && a[0] != '-') list->push_back(argv[i]);
+        else { fprintf(stderr, "error: unexpected argument '%s'\n%s", a.c_str(), use); return 2; }
+    }
+    if (dir.empty() || gfas.empty()) { fprintf(stderr, "%s", use); return 2; }
+    fprintf(stderr, "\nStarting autocycler combine\nSettings:\n  --autocycler_dir %s\n  --in_gfas %s\n", dir.c_str(), gfas[0]);
+    for (size_t i = 1; i < gfas.size(); i++) fprintf(stderr, "            %s\n", gfas[i]);
+    if (!reads.empty()) {
+        fprintf(stderr, "  --reads %s\n", reads[0]);
+        for (size_t i = 1; i < reads.size(); i++) fprintf(stderr, "          %s\n", reads[i]);
+        fprintf(stderr, "  --depth_kmer %u\n", depth_kmer);
+    }
+    char* report = nullptr;
+    if (ac_combine(dir.c_str(), gfas.data(), (uint32_t)gfas.size(), reads.empty() ? nullptr : reads.data(), (uint32_t)reads.size(), depth_kmer, device, &report) != 0) {
+        fprintf(stderr, "\nError: %s\n", ac_last_error());
+        return 1;
+    }
+    fprintf(stderr, "\n%s", report ? report : "");
+    ac_string_free(report);
+    fprintf(stderr, "\nFinished!\nCombined graph: %s/consensus_assembly.gfa\nCombined fasta: %s/consensus_assembly.fasta\n\n", dir.c_str(), dir.c_str());
+    return 0;
+}
+
+// `autocycler gfa2fasta` (main.rs: Gfa2fasta): -i/--in_gfa FILE  -o/--out_fasta FILE  [--device 0]
+static int gfa2fasta_main(int argc, char** argv) {
+    std::string in, out;
+    int device = 0;
+    const char* use = "Usage: autocycler-compress gfa2fasta --in_gfa <GFA> --out_fasta <FASTA> [--device 0]\n";
+    for (int i = 2; i < argc; i++) {
+        std::string a = argv[i];
+        auto val = [&]() -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", a.c_str()); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-i" || a == "--in_gfa") in = val();
+        else if (a == "-o" || a == "--out_fasta") out = val();
+        else if (a == "--device") device = atoi(val());
+        else { fprintf(stderr, "error: unexpected argument '%s'\n%s", a.c_str(), use); return 2; }
+    }
+    if (in.empty() || out.empty()) { fprintf(stderr, "%s", use); return 2; }
+    fprintf(stderr, "\nStarting autocycler gfa2fasta\nSettings:\n  --in_gfa %s\n  --out_fasta %s\n\n", in.c_str(), out.c_str());
+    uint64_t counts[3] = {0, 0, 0};
+    if (ac_gfa2fasta(in.c_str(), out.c_str(), device, counts) != 0) {
+        fprintf(stderr, "\nError: %s\n", ac_last_error());
+        return 1;
+    }
+    const char* what[3] = {"circular", "linear", "other"};
+    for (int c = 0; c < 3; c++) fprintf(stderr, "%llu %s sequence%s\n", (unsigned long long)counts[c], what[c], counts[c] == 1 ? "" : "s");
+    fprintf(stderr, "\nFinished!\n\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "decompress") == 0) return decompress_main(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "combine") == 0) return combine_main(argc, argv);
+    if (argc > 1 && strcmp(argv[1], "gfa2fasta") == 0) return gfa2fasta_main(argc, argv);
     if (argc > 1 && strcmp(argv[1], "trim") == 0) return cluster_dir_main(argc, argv, true);
     if (argc > 1 && strcmp(argv[1], "resolve") == 0) return cluster_dir_main(argc, argv, false);
     if (argc > 1 && strcmp(argv[1], "clean") == 0) return clean_main(argc, argv);

@@ -21,6 +21,7 @@
 #include "finish_host.hpp"
 #include "apply_host.hpp"
 #include "clean_host.hpp"
+#include "combine_host.hpp"
 #include "cluster_host.hpp"
 #include "cluster_qc_host.hpp"
 
@@ -271,6 +272,10 @@ void apply_bridges_device(const ApplyInput& in, const ApplyPlan& plan, ApplyResu
 // entries the device gathers) and remove_low_depth_unitigs in rounds.  in: checked by clean_prepare.  Fills the per-unitig arrays over
 // n_unitigs + 2 per duplication, the links in get_links_for_gfa order, the rounds and the stats.  n_unitigs > 0.
 void clean_device(const CleanInput& in, CleanResult* out);
+// `autocycler combine`'s graph order, offsets, flags, topology and L-line order (combine.rs:144-224) on the device (kernels_combine.inc), for the
+// concatenation of in.n_graphs graphs.  in: checked by combine_prepare; at least one unitig.  Fills the cluster and unitig records and the links
+// in output order and the stats; combine_finish does the rest.
+void combine_device(const CombineInput& in, CombineResult* out);
 // device_prims.hpp against std:: on n pseudo-random items (tests); throws on a mismatch.
 void primitives_selftest(uint64_t n, uint64_t seed, int end_bit, int key_kind);
 // One primitive of device_prims.hpp / wave_rt.hpp on the caller's arrays (tests: the reference is the test's own): selftest_prims.inc.

@@ -4,7 +4,7 @@
 // (kernels_components.inc); the linear-path merge plan (kernels_merge.inc); sequence subsets and the paths over merged unitigs (kernels_subset.inc);
 // the finished graph after a merge: order, renumbering, L lines (kernels_finish.inc); resolve's apply_bridges with its removals (kernels_apply.inc);
 // clean's removal, duplication and low-depth rounds (kernels_clean.inc); trim's slices, length check and exclusion feeding the subset stages
-// (kernels_trim_apply.inc).
+// (kernels_trim_apply.inc); combine's graph order, offsets, per-unitig end tests and L-line order over all clusters at once (kernels_combine.inc).
 #include "graph_impl.hpp"
 
 namespace ac {
@@ -22,5 +22,6 @@ namespace ac {
 #include "kernels_finish.inc"  // ac_merge_finish / ac_subsets_finish: the S-line order, renumber_unitigs, the L and P lines after a merge (f-12)
 #include "kernels_apply.inc"   // ac_apply_bridges / ac_graph_resolve_apply: apply_bridges, reduce_depths and the two removals of `autocycler resolve` (f-13)
 #include "kernels_clean.inc"   // ac_clean_graph / ac_graph_clean: remove, duplicate and remove_low_depth_unitigs of `autocycler clean` (f-14)
+#include "kernels_combine.inc" // ac_combine_graphs / ac_combine_handles: load_clusters' order, combine_clusters' offsets, topology and get_links_for_gfa of `autocycler combine` (f-16)
 
 }  // namespace ac

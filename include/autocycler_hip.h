@@ -966,6 +966,96 @@ int ac_trim_dir(const char* cluster_dir, double min_identity, uint32_t max_uniti
  * 5_final.gfa through ac_resolve_graphs. */
 int ac_resolve_dir(const char* cluster_dir, int device);
 
+/* `autocycler combine` (combine.rs:28-54) and `autocycler gfa2fasta` (gfa2fasta.rs:56-83): the clusters' final graphs gathered into
+ * consensus_assembly.gfa, .fasta and .yaml.  Additions of ABI generation 13, found by name; AC_ABI_VERSION stays 13.  Read-only.
+ * The input is the concatenation of n_graphs graphs (an empty graph is legal):
+ *   unitig_off, link_off   n_graphs + 1 words each, from 0, ascending: a graph's unitigs and links in the arrays below
+ *   number     per unitig its own number (any order, holes allowed; two unitigs of one graph with one number are an error: the reference's
+ *              index would silently keep the last)
+ *   links      one entry per L line in L-line order: signed 1-based FILE-ORDER INDICES within their graph (not numbers).  An entry that is
+ *              0 or beyond its graph is an error.
+ *   depth, type   DP:f and AC_UNITIG_* per unitig, or NULL (0 / Other)
+ *   read_depth, has_read_depth   both or neither: with them the result is that of `combine --reads` (has_read_depth 0 = the reference's
+ *              None); what ac_depth_finish writes goes straight in
+ *   seq_bytes, seq_begin   both or neither: the unitigs' bytes, kept for the texts only.  They are never sent to the device: no decision
+ *              reads them.
+ * The graphs come out in order of total length, descending, ties in input order (load_clusters' stable sort); a unitig prints as its number
+ * plus its graph's offset, the sum of max_unitig_number() over the graphs before it (the maximum, not the count); a graph's links in
+ * get_links_for_gfa order: per unitig in file order its forward list, then its reverse list, each in L-line order.
+ * The number of launches depends on the bits of twice the number of unitigs (the link sort's key) and on nothing else.
+ * Errors (return 1, ac_last_error; never an abort): no graph; null pointers; offsets that do not ascend; "combine: graph G: unitig number
+ * N occurs more than once" (the lowest such (G, N)); "combine: graph G: offset O + its highest unitig number M does not fit 32 bits" (the
+ * first such graph in output order); "combine: graph G: link I (a -> b) names no unitig of its graph" (the lowest such link); "combine:
+ * graph G: the total of bases reaches 2^46 with this graph".  G is the graph's place in the caller's list, from 0. */
+typedef struct ac_combined ac_combined;
+typedef struct {
+    uint32_t input_index;           /* the graph's place in the caller's list */
+    uint32_t unitigs;
+    uint64_t length, links;         /* total_length(); entries of its link list */
+    uint64_t offset;                /* added to its numbers */
+    uint32_t max_number;            /* max_unitig_number(); 0 for an empty graph */
+    uint32_t topology;              /* AC_TOPOLOGY_* (ac_topology_name) */
+    uint32_t has_read_depth;        /* cluster_depth (combine.rs:107-119) is Some */
+    uint32_t reserved;
+    double read_depth;              /* cluster_depth: sum of depth * length over sum of length, over the unitigs that have a depth, in unitig order */
+} ac_combined_cluster;
+typedef struct {
+    uint32_t graph, index;          /* the input index of its graph; its place in that graph's file order, from 0 */
+    uint32_t number, length;        /* printed number: its own + the graph's offset */
+    double depth;                   /* printed in DP:f: the caller's depth; with read depths the read depth, 0.0 where there is none */
+    double read_depth;              /* 0 where has_read_depth is 0 */
+    uint8_t has_read_depth;
+    uint8_t flags;                  /* as ac_components_unitig_flags: 1 open start, 2 open end, 4 hairpin start, 8 hairpin end, 16 isolated and circular, 32 isolated and linear */
+    uint8_t type;                   /* AC_UNITIG_* */
+    uint8_t reserved[5];
+} ac_combined_unitig;
+typedef struct {
+    uint32_t size;                  /* the library's sizeof(ac_combined_summary) */
+    uint32_t graphs;
+    uint64_t bases, unitigs, links; /* consensus_assembly_bases, consensus_assembly_unitigs */
+    uint32_t fully_resolved;        /* every graph has exactly one unitig */
+    uint32_t with_reads;
+    uint32_t launches, read_backs;
+    double seconds_device;          /* the kernels of the call, by device events */
+} ac_combined_summary;
+int ac_combine_graphs(uint32_t n_graphs, const uint64_t* unitig_off, const uint64_t* link_off, const uint32_t* number, const uint32_t* unitig_len,
+        const double* depth /* or NULL */, const uint8_t* type /* or NULL */, const ac_link* links, const double* read_depth, const uint8_t* has_read_depth /* both or NULL */,
+        const uint8_t* seq_bytes, const uint64_t* seq_begin /* both or NULL */, int device, ac_combined** out);
+/* The same on graph handles (ac_graph_from_gfa of each 5_final.gfa: numbers 1, 2, 3, ...).  type, read_depth, has_read_depth: one array per
+ * graph (an entry may be NULL for a graph without unitigs; type[g] NULL = Other), or NULL.  The bytes are copied into the object. */
+int ac_combine_handles(const ac_graph* const* graphs, uint32_t n_graphs, const uint8_t* const* type, const double* const* read_depth,
+        const uint8_t* const* has_read_depth, int device, ac_combined** out);
+/* The arrays belong to the object.  Clusters and unitigs in output order; the links carry printed numbers, graph after graph. */
+int ac_combined_clusters(const ac_combined*, const ac_combined_cluster** clusters, uint32_t* n);
+int ac_combined_unitigs(const ac_combined*, const ac_combined_unitig** unitigs, uint64_t* n);
+int ac_combined_links(const ac_combined*, const ac_link** links, uint64_t* n);
+size_t ac_combined_summary_get_sized(const ac_combined*, ac_combined_summary* out, size_t out_size);
+void ac_combined_free(ac_combined*);
+/* consensus_assembly.gfa ("H\tVN:Z:1.0", S lines with DP:f to two decimals and colour_tag(true), each graph's L lines behind its S lines),
+ * consensus_assembly.fasta (">N length=L[ depth=D| depth=unavailable][ circular=true topology=circular| circular=false topology=linear]")
+ * and consensus_assembly.yaml (CombineMetrics, metrics.rs:234-248, serde_yaml 0.9 block style).  The first two need the bytes.  The depth
+ * lines are what combine.rs:94-104 prints on stderr (empty without reads).  *out is malloc'ed (ac_string_free). */
+int ac_combined_gfa_string(const ac_combined*, char** out, uint64_t* len /* may be NULL */);
+int ac_combined_fasta_string(const ac_combined*, char** out, uint64_t* len /* may be NULL */);
+int ac_combined_yaml_string(const ac_combined*, char** out, uint64_t* len /* may be NULL */);
+int ac_combined_depth_lines(const ac_combined*, char** out, uint64_t* len /* may be NULL */);
+/* From the texts of the cluster GFAs to the three texts.  The loader is combine's own (UnitigGraph::from_gfa_file as combine uses it): segment
+ * numbers in any order and with holes, L lines attached in file order, an L line naming a segment the file lacks dropped, the S lines' CL:Z
+ * colours kept, H and P lines ignored.  read_depth, has_read_depth: one array per graph in file order, or both NULL.  summary may be NULL
+ * (its size field set by the caller, 0 = the library's).  The three texts are malloc'ed (ac_string_free each). */
+int ac_combine_gfas(const char* const* texts, const uint64_t* lens, uint32_t n, const double* const* read_depth, const uint8_t* const* has_read_depth, int device,
+        char** gfa, uint64_t* gfa_len, char** fasta, uint64_t* fasta_len, char** yaml, uint64_t* yaml_len /* lengths may be NULL */, ac_combined_summary* summary);
+/* The whole command: every file must exist; with reads (n_reads > 0) depth_kmer must be odd and 11 .. 31 and the reads are counted against
+ * all graphs together (ac_depth_begin / ac_depth_add_fastq / ac_depth_finish: one table, as the reference).  Creates autocycler_dir when it is
+ * missing and writes consensus_assembly.gfa, .fasta and .yaml, each through a temporary file and a rename.  report, when given, receives
+ * the depth lines followed by one line saying whether the assembly is fully resolved (malloc'ed, ac_string_free). */
+int ac_combine(const char* autocycler_dir, const char* const* in_gfas, uint32_t n_gfas, const char* const* reads, uint32_t n_reads, uint32_t depth_kmer, int device,
+        char** report /* may be NULL */);
+/* `autocycler gfa2fasta`: one graph, no offset, unitigs with an empty sequence skipped, ">N length=L depth=D[ circular=...]" with the file's
+ * DP:f to one decimal.  counts, when given, receives the circular, linear and other sequences.  *fasta is malloc'ed (ac_string_free). */
+int ac_gfa2fasta_string(const char* gfa_text, uint64_t len, int device, char** fasta, uint64_t* fasta_len /* may be NULL */, uint64_t* counts /* 3, may be NULL */);
+int ac_gfa2fasta(const char* in_gfa, const char* out_fasta, int device, uint64_t* counts /* 3, may be NULL */);
+
 /* The UPGMA tree of `autocycler cluster` and what the reference derives from it, up to the point where clusters are scored and written.
  * The merge loop of upgma (cluster.rs:395-458 with get_closest_pair :461-480) runs on the device: S - 1 merges, each three launches over a
  * nearest-neighbour cache per row, nothing read by the host in between.  Sequences are rows in ascending id order.
@@ -1279,7 +1369,10 @@ const char* ac_version(void);
  *      ac_cleaned_merge_plan, ac_cleaned_finish, ac_cleaned_gfa_string, ac_parse_tig_numbers, ac_gfa_segment_types, ac_clean_gfa, ac_clean
  *      with ac_cleaned_summary and the AC_CLEAN_* values; then, likewise: ac_trim_apply, ac_graph_trim_apply, ac_graph_trim,
  *      ac_trimmed_records, ac_trimmed_summary_get_sized, ac_trimmed_free, ac_trimmed_subsets, ac_trimmed_finish, ac_trimmed_yaml_string,
- *      ac_trim_gfa, ac_trim_dir, ac_resolve_dir with ac_trimmed_record, ac_trimmed_summary and the AC_TRIM_CHOOSE_* values. */
+ *      ac_trim_gfa, ac_trim_dir, ac_resolve_dir with ac_trimmed_record, ac_trimmed_summary and the AC_TRIM_CHOOSE_* values; then, likewise: ac_combine_graphs,
+ *      ac_combine_handles, ac_combined_clusters, ac_combined_unitigs, ac_combined_links, ac_combined_summary_get_sized, ac_combined_free,
+ *      ac_combined_gfa_string, ac_combined_fasta_string, ac_combined_yaml_string, ac_combined_depth_lines, ac_combine_gfas, ac_combine,
+ *      ac_gfa2fasta_string, ac_gfa2fasta with ac_combined_cluster, ac_combined_unitig and ac_combined_summary. */
 #define AC_ABI_VERSION 13
 int ac_abi_version(void);
 const char* ac_source_hash(void);   /* 16 hex digits: digest of the sources this library was built from (csrc/Makefile; tools/source_hash.py) */
