@@ -8,7 +8,9 @@ per unitig (merge_util.MergeGraph).
   remove_low_depth_unitigs     :670-721: the reverse walk over `unitigs`, each decision against the lists as the deletions before it left them
   then                         merge_util (through finish_util.model_graph), finish_util.finish_model and finish_util.save_gfa, unedited
 It shares no code with kernels_clean.inc or clean_host.cpp, and states no rule about rounds, neighbourhoods or where created links land: all of
-that is read off the lists."""
+that is read off the lists.  The literal walk rebuilds the unitig list, the index and every list per deletion and is quadratic; clean_model_fast
+makes the same decisions in the same order on lists edited in place, for the sizes the literal one cannot afford, and is held equal to it on
+every case the literal one can."""
 import json
 import math
 
@@ -165,6 +167,143 @@ def clean_model(n, links, lens, depths=None, types=None, alive=None, seqs=None, 
     return dict(n_out=n_out, len=[int(x) for x in lens] + [len(u.forward_seq) for u in copies], alive=[int(u in graph.unitig_index) for u in range(1, n_out + 1)],
                 depth=depth_in + [u.depth for u in copies], type=type_in + [u.unitig_type for u in copies], copy_of=[0] * n + [u.copy_of for u in copies], reason=reason,
                 links=get_links_for_gfa(graph), graph=graph, seqs=[everyone[u].forward_seq if u in everyone else b"" for u in range(1, n_out + 1)])
+
+
+# ---- the same decisions on lists that are edited in place --------------------------------------------------------------------------------------
+class FastUnitig:
+    """one unitig of clean_model_fast: what Unitig holds, and whether it is still among `unitigs`"""
+    __slots__ = ("number", "forward_seq", "depth", "unitig_type", "copy_of", "here", "forward_next", "forward_prev", "reverse_next", "reverse_prev")
+
+    def __init__(self, number, forward_seq, depth, unitig_type, copy_of=0):
+        self.number, self.forward_seq, self.depth, self.unitig_type, self.copy_of, self.here = number, forward_seq, depth, unitig_type, copy_of, True
+        self.forward_next, self.forward_prev, self.reverse_next, self.reverse_prev = [], [], [], []
+
+    def lists(self):
+        return (self.forward_next, self.forward_prev, self.reverse_next, self.reverse_prev)
+
+
+class FastGraph:
+    """what cleaned_text reads of a graph: `unitigs` in their order"""
+
+    def __init__(self, unitigs):
+        self.unitigs = unitigs
+
+
+def _take_out(by_number, u):
+    """retain + delete_dangling_links for one unitig: it leaves `unitigs` with its own lists as they are (nobody walks them again but
+    duplicate_unitig_by_number, which wants them so), and every list that names it loses those entries, the others keeping their order"""
+    u.here = False
+    for num in {e[0] for lst in u.lists() for e in lst if e[0] != u.number}:
+        for lst in by_number[num].lists():
+            if any(e[0] == u.number for e in lst):
+                lst[:] = [e for e in lst if e[0] != u.number]
+
+
+def _push_link(by_number, start_num, end_num):
+    """create_link: both directions at the end of their lists, a link that is its own mirror image once"""
+    for a, b in ((start_num, end_num),) if start_num == -end_num else ((start_num, end_num), (-end_num, -start_num)):
+        start, end = by_number[abs(a)], by_number[abs(b)]
+        (start.forward_next if a > 0 else start.reverse_next).append((abs(b), b > 0))
+        (end.forward_prev if b > 0 else end.reverse_prev).append((abs(a), a > 0))
+
+
+def clean_model_fast(n, links, lens, depths=None, types=None, alive=None, seqs=None, remove=(), duplicate=(), min_depth=None, name="the graph", counts=None):
+    """clean_model's decisions in clean_model's order — the removals, the duplications ascending, the reverse walk over `unitigs` with the copies
+    first, b before a — on alive flags and per-unitig lists edited in place: a decision costs the unitig's own and its neighbours' lists, not the
+    graph.  Its only justification is that it equals clean_model wherever that one is affordable (test_clean_emu.py asserts it on every case at
+    or below 4097 unitigs).  -> the same dict, `graph` holding `unitigs` alone; counts (a dict, optional) receives n_edit, the entries after the
+    duplications, edited, those entries, and n_candidates, the unitigs the walk does not skip"""
+    remove, duplicate = sorted(remove), sorted(duplicate)
+    by_number = {}
+    for u in range(1, n + 1):
+        if alive is None or alive[u - 1]:
+            by_number[u] = FastUnitig(u, bytes(seqs[u - 1]) if seqs is not None else b"N" * int(lens[u - 1]), float(depths[u - 1]) if depths is not None else 0.0,
+                                      int(types[u - 1]) if types is not None else M.OTHER)
+    for a, b in links:      # build_links_from_gfa: line order
+        x, y = abs(int(a)), abs(int(b))
+        if not (0 < x <= n and 0 < y <= n):
+            raise ValueError(f"link refers to nonexistent unitig: {y if 0 < x <= n else x}")
+        start, end = by_number.get(x), by_number.get(y)
+        if start is not None and end is not None:
+            (start.forward_next if a > 0 else start.reverse_next).append((y, b > 0))
+            (end.forward_prev if b > 0 else end.reverse_prev).append((x, a > 0))
+    for tig in remove + duplicate:
+        if tig not in by_number:
+            raise CleanError(f"{name} does not contain tig {tig}")
+    reason = [KEPT if u in by_number else ABSENT for u in range(1, n + 1)]
+    for tig in remove:
+        if by_number[tig].here:
+            _take_out(by_number, by_number[tig])
+        reason[tig - 1] = REMOVED
+    copies = []
+    for tig in duplicate:
+        target = by_number[tig]
+        if not target.here:
+            raise CleanError(f"unitig {tig} no longer exists: it was removed or duplicated earlier in the same call")
+        if len([e for e in target.forward_next + target.reverse_next if e[0] != tig]) != 2:
+            raise CleanError(f"unitig {tig} does not contain exactly two non-self links")
+        a_num = n + len(copies) + 1      # (max + 1: the copies before this one are all still there)
+        b_num = a_num + 1
+        for num in (a_num, b_num):
+            by_number[num] = FastUnitig(num, target.forward_seq, target.depth / 2.0, target.unitig_type, tig)
+            copies.append(by_number[num])
+        _take_out(by_number, target)
+        for lst, sign in ((target.forward_next, 1), (target.reverse_next, -1)):
+            for number, strand in lst:
+                if number == tig:
+                    _push_link(by_number, sign * a_num, a_num if strand else -a_num)
+                    _push_link(by_number, sign * b_num, b_num if strand else -b_num)
+        others = [(tig, x if s else -x) for x, s in target.forward_next if x != tig] + [(-tig, x if s else -x) for x, s in target.reverse_next if x != tig]
+        for (start, end), new in zip(others, (a_num, b_num)):
+            swap = lambda x: new if x == tig else -new if x == -tig else x
+            _push_link(by_number, swap(start), swap(end))
+        reason[tig - 1] = DUPLICATED
+    n_out = n + len(copies)
+    reason += [KEPT] * len(copies)
+    walk = [by_number[u] for u in sorted(by_number) if by_number[u].here]      # `unitigs`: the originals ascending, then the copies
+    if counts is not None:
+        counts["edited"] = [(x, b if s else -b) for u in walk for x, lst in ((u.number, u.forward_next), (-u.number, u.reverse_next)) for b, s in lst]
+        counts["n_edit"] = len(counts["edited"])
+        counts["n_candidates"] = sum(1 for u in walk if not u.depth > min_depth) if min_depth is not None else 0
+    if min_depth is not None:
+        for u in reversed(walk):
+            if u.depth > min_depth:
+                continue
+            ok_to_delete = True
+            for mine, theirs in ((u.forward_next, ("forward_prev", "reverse_prev")), (u.forward_prev, ("forward_next", "reverse_next"))):
+                for num, strand in mine:
+                    if num == u.number:
+                        continue
+                    if not any(x != u.number for x, _ in getattr(by_number[num], theirs[0] if strand else theirs[1])):
+                        ok_to_delete = False
+                        break
+                if not ok_to_delete:
+                    break
+            if ok_to_delete:
+                _take_out(by_number, u)
+                reason[u.number - 1] = LOW_DEPTH
+            else:
+                reason[u.number - 1] = KEPT_DEAD_END
+    left = [u for u in walk if u.here]
+    out_links = []
+    for u in left:      # get_links_for_gfa
+        out_links += [(u.number, b if s else -b) for b, s in u.forward_next]
+        out_links += [(-u.number, b if s else -b) for b, s in u.reverse_next]
+    depth_in = [float(depths[u]) if depths is not None else 0.0 for u in range(n)]
+    type_in = [int(types[u]) if types is not None else M.OTHER for u in range(n)]
+    return dict(n_out=n_out, len=[int(x) for x in lens] + [len(u.forward_seq) for u in copies], alive=[int(u in by_number and by_number[u].here) for u in range(1, n_out + 1)],
+                depth=depth_in + [u.depth for u in copies], type=type_in + [u.unitig_type for u in copies], copy_of=[0] * n + [u.copy_of for u in copies], reason=reason,
+                links=out_links, graph=FastGraph(left), seqs=[by_number[u].forward_seq if u in by_number else b"" for u in range(1, n_out + 1)])
+
+
+def assert_models_equal(fast, literal, what=""):
+    """every key but `graph`, of which the unitigs that are left and what save_gfa prints of them"""
+    for key in ("n_out", "len", "alive", "type", "copy_of", "reason", "links", "seqs"):
+        assert fast[key] == literal[key], (what, key)
+    import numpy as np
+    assert np.asarray(fast["depth"], dtype=np.float64).tobytes() == np.asarray(literal["depth"], dtype=np.float64).tobytes(), (what, "depth")
+    of = lambda g: [(u.number, u.forward_seq, repr(u.depth), u.unitig_type) for u in g.unitigs]
+    assert of(fast["graph"]) == of(literal["graph"]), (what, "unitigs")
 
 
 def cleaned_text(exp, k, use_other_colour=True):

@@ -3,7 +3,9 @@
   kernels_clean.inc: the emulation linked into tests/c_client/clean_bounds_check.cpp with the guarded arena of csrc/device_rt.hpp
   (AC_ARENA_GUARD: exact sizes and red zones; level 2 also poisons rewound memory), from the per-level objects of `make kernel_bounds_check`,
 both under the address and undefined-behaviour sanitizers.  The named cases and the boundary table of test_clean_emu.py are replayed at both
-levels: exit status 0, no sanitizer report, and every result equal to the model's.  `make clean_bounds_check` in csrc builds the same programs.
+levels: exit status 0, no sanitizer report, and every result equal to the model's — the tile, key-width, multi-arm and dense rows included, with
+the counts that make them those rows (check_row); a buffer sized by the links, the edited entries or n_out would be overrun at a tile's edge.
+`make clean_bounds_check` in csrc builds the same programs.
 Nothing is loaded into Python and nothing is preloaded."""
 import fcntl
 import re
@@ -16,7 +18,7 @@ import pytest
 import bounds_cases as B
 import clean_util as CU
 import emu_lib
-from test_clean_emu import K, boundary_cases, named_cases, run_model
+from test_clean_emu import K, TEXTS_MAX, boundary_cases, boundary_expected, check_row, hub_case, named_cases, run_model, run_model_fast
 
 LEVELS = [1, 2]
 # the rounds between two read-backs, from the source (test_clean_emu.py reads the same number from the library's summary)
@@ -59,10 +61,12 @@ def seq_block(seqs):
     return np.frombuffer(b"".join(seqs), dtype=np.uint8), begin      # (an exact block: no byte behind the last unitig)
 
 
-def add_call(calls, case, label):
-    exp = run_model(case)
+def add_call(calls, case, label, exp=None, facts=None):
+    """exp, facts: a row of the boundary table brings its model and what check_row holds it to; the rows above TEXTS_MAX unitigs go without texts"""
+    exp = run_model(case) if exp is None else exp
     nan = CU.has_nan_alive(exp)
-    texts = 0 if nan else 1 if CU.is_multiset(exp) else 2
+    texts = 0 if nan or case["n"] > TEXTS_MAX else 1 if CU.is_multiset(exp) else 2
+    name = label
     want_edited = CU.cleaned_text(exp, K, True) if texts >= 1 else b""
     want_final = CU.final_text(exp, K) if texts >= 2 else b""
     sb, sg = seq_block(case["seqs"])
@@ -78,8 +82,10 @@ def add_call(calls, case, label):
         assert np.frombuffer(outs[7], dtype="<u8").tolist() == [begin[(c or u + 1) - 1] for u, c in enumerate(exp["copy_of"])], (label, "seq_begin")
         assert bytes(outs[8]) == want_edited and bytes(outs[9]) == want_final, (label, "texts")
         rounds = int(np.frombuffer(outs[10], dtype="<u8")[0])
-        if label.startswith("chain of"):
+        if name.startswith("chain of"):
             assert rounds == case["n"], label
+        if facts is not None:
+            check_row(name, case, facts, rounds, BATCH)
     calls.add("clean", [case["n"], len(case["links"]), len(case["remove"]), len(case["duplicate"]), int(case["min_depth"] is not None),
                         B.f64_bits(case["min_depth"] if case["min_depth"] is not None else 0.0), texts],
               [B.arr(np.asarray(case["links"], dtype=np.int32).reshape(-1, 2), np.int32), B.arr(case["lens"], np.uint32), B.arr(case["depths"], np.float64),
@@ -97,7 +103,7 @@ def named_calls():
 def boundary_calls():
     calls = B.Calls()
     for name, case in boundary_cases(BATCH).items():
-        add_call(calls, case, name)
+        add_call(calls, case, name, *boundary_expected(BATCH, name))
     return calls
 
 
@@ -116,3 +122,14 @@ def test_named_cases(exe, tmp_path):
 
 def test_boundary_table(exe, tmp_path):
     assert _calls("boundary", boundary_calls).run(exe, tmp_path) == len(boundary_cases(BATCH))
+
+
+def hub_calls():
+    calls, hub = B.Calls(), hub_case(4097)
+    add_call(calls, hub, "hub of degree 4097", run_model_fast(hub))
+    return calls
+
+
+def test_hub_of_degree_4097(exe, tmp_path):
+    """not a row of the table (the device is spared its 9258 launches): a range off[2u] .. off[2u + 2] of 4097 entries and 513 batches, 6 s per level"""
+    assert _calls("hub", hub_calls).run(exe, tmp_path) == 1

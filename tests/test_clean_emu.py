@@ -2,7 +2,8 @@
 ac_clean on the CPU emulation of the shipped kernels (kernels_clean.inc) against the literal Python model of clean_util.py: removal, the
 sequential duplication with its list pushes, the reverse walk of remove_low_depth_unitigs, then merge_util, finish_util.finish_model and
 finish_util.save_gfa for the texts.  Every comparison is equality (depths bit for bit, link order included).  The same checks run on the
-device in test_clean_gpu.py."""
+device in test_clean_gpu.py.  The boundary table's rows beyond one wavefront (tile sizes, wide keys, rounds side by side) are judged by
+clean_util.clean_model_fast, which the tests here hold equal to the literal model wherever that one is affordable."""
 import ctypes
 import math
 import random
@@ -63,15 +64,27 @@ def run_model(case):
     return CU.clean_model(case["n"], case["links"], case["lens"], case["depths"], case["types"], case["alive"], case["seqs"], case["remove"], case["duplicate"], case["min_depth"])
 
 
-def check_case(case, lib_path, device=0, what=""):
-    """one graph: the arrays, reasons and link order, the edited graph's text, and the merged graph with its text against the model -> (model, summary)"""
-    exp = run_model(case)
+def run_model_fast(case, counts=None):
+    """clean_util.clean_model_fast: the judge where the literal model is not affordable, held equal to it where it is (test_fast_model_*)"""
+    return CU.clean_model_fast(case["n"], case["links"], case["lens"], case["depths"], case["types"], case["alive"], case["seqs"], case["remove"], case["duplicate"],
+                               case["min_depth"], counts=counts)
+
+
+def check_case(case, lib_path, device=0, what="", texts=True, exp=None):
+    """one graph: the arrays, reasons and link order, the edited graph's text, and the merged graph with its text against the model -> (model, summary).
+    texts=False: the arrays, reasons, depths bit for bit, link order and summary only (no Python merge, finish or save_gfa); exp: the model's
+    result where the caller has it already"""
+    exp = run_model(case) if exp is None else exp
     cl = run_library(case, lib_path, device)
     assert isinstance(cl, Cleaned) and cl.n_unitigs == case["n"]
     CU.assert_same(cl, exp, what)
     seq_begin = [0] + np.cumsum(case["lens"]).tolist()[:-1] if case["n"] else []
     assert ([] if cl.seq_begin is None else cl.seq_begin.tolist()) == [seq_begin[(c or u + 1) - 1] for u, c in enumerate(exp["copy_of"])], (what, "seq_begin")
     assert cl.summary["rounds_per_batch"] >= 2 and cl.summary["links_in"] == len(case["links"])
+    if not texts:
+        sm = cl.summary
+        cl.close()
+        return exp, sm
     if not CU.has_nan_alive(exp):      # (a NaN depth prints differently in Rust, C and Python: the arrays above have compared it)
         for colour in (False, True):
             assert cl.gfa(K, use_other_colour=colour) == CU.cleaned_text(exp, K, colour), (what, "text of the edited graph")
@@ -241,7 +254,188 @@ def candidates_case(count):
     return make_case(4 * count, links, depths=depths, min_depth=1.0)
 
 
+# ---- rows beyond one wavefront: the tiles of device_prims.hpp (RS_TILE = 2048, SCAN_TILE = 4096), the key widths, rounds side by side ----------------
+TILE_SIZES = (2047, 2048, 2049, 4095, 4096, 4097)
+LITERAL_MAX = 4097      # up to here the literal model judges or is compared with the fast one; above it clean_model_fast alone
+TEXTS_MAX = 4097        # up to here the Python merge, finish and save_gfa are run as well
+
+
+def bit_width(x):
+    return int(x).bit_length()
+
+
+def tile_case(seed, n, nl=None, ne=None, candidates=None, n_remove=50, n_dup=40, link_factor=1.3, low=1 / 3, special=0.02):
+    """a random closed graph of n unitigs: about link_factor links per unitig, `special` of them loops and hairpins, n_remove removals, n_dup
+    duplications of pairwise non-adjacent duplicable unitigs without a loop (a quarter of them of a depth whose half is low), about `low` of the
+    unitigs low.  nl, ne, candidates: the exact number of link entries, of entries after the duplications, of low unitigs the walk meets — links
+    between unitigs that are neither removed nor duplicated are added until nl or ne holds (a hairpin for an odd rest).  The caller states the
+    counts it wants as case["expect"]; check_row asserts them."""
+    rng = random.Random(seed)
+    signed = lambda: rng.randint(1, n) * rng.choice((1, -1))
+    links = {}
+
+    def add(a, b):
+        links[(a, b)] = links[(-b, -a)] = True
+
+    factor = link_factor if nl is None and ne is None else link_factor - 0.05      # (below the target: the rest is added)
+    for _ in range(int(factor * n)):
+        a = signed()
+        add(a, (a if rng.random() < 0.5 else -a) if rng.random() < special else signed())
+    remove = sorted(rng.sample(range(1, n + 1), n_remove))
+    gone = set(remove)
+    others, loop = [[] for _ in range(n + 1)], [False] * (n + 1)
+    for a, b in links:
+        if abs(a) in gone or abs(b) in gone:
+            continue
+        if abs(a) == abs(b):
+            loop[abs(a)] |= a == b
+        else:
+            others[abs(a)].append(abs(b))
+    able = [u for u in range(1, n + 1) if u not in gone and len(others[u]) == 2 and not loop[u]]
+    rng.shuffle(able)
+    duplicate, near = [], set()
+    for u in able:
+        if len(duplicate) < n_dup and u not in near:
+            duplicate.append(u)
+            near |= {u} | set(others[u])
+    assert len(duplicate) == n_dup, "too few duplicable unitigs: another seed"
+    low_dups = set(duplicate[:n_dup // 4])
+    free = [u for u in range(1, n + 1) if u not in gone and u not in duplicate]
+    n_low = (round(low * n) if candidates is None else candidates) - 2 * len(low_dups)
+    low_set = set(rng.sample(free, n_low))
+    depths = [1.5 if u in low_dups else 9.0 if u in duplicate else 0.5 if u in low_set else rng.choice((0.0, 0.5, 1.0)) if u in gone else rng.choice((1.5, 7.0, 20.0))
+              for u in range(1, n + 1)]
+    case = lambda: make_case(n, list(links), depths=depths, lens=[1 + (u * 7) % 6 for u in range(n)], types=[(u * 5 + u // 3) % 4 for u in range(n)], remove=remove,
+                             duplicate=sorted(duplicate), min_depth=1.0)
+    if nl is not None or ne is not None:
+        counts = {}
+        if ne is not None:
+            run_model_fast(dict(case(), min_depth=None), counts)
+        rest = nl - len(links) if nl is not None else ne - counts["n_edit"]
+        assert rest >= 0, "the base graph is above the target: a lower link_factor"
+        while rest:
+            a, b = signed(), signed()
+            if abs(a) in gone or abs(b) in gone or abs(a) in duplicate or abs(b) in duplicate or (a, b) in links:
+                continue
+            if rest == 1:
+                b = -a
+            elif abs(a) == abs(b):
+                continue
+            if (a, b) in links:
+                continue
+            add(a, b)
+            rest -= 1 if a == -b else 2
+    return case()
+
+
+def multi_arm_case(bubbles, arms, seed=31, spare=0):
+    """`bubbles` bubbles of `arms` low arms and one high arm between the same two ends, the numbers dealt in a shuffled order, random strands: the
+    arms of one bubble lie within distance two of each other, so one goes per round; the high arm keeps every end off a dead end, so all go.
+    spare: as many high unitigs without a link among them (they widen the keys and nothing else)"""
+    rng = random.Random(seed)
+    n = bubbles * (arms + 3) + spare
+    numbers = list(range(1, n + 1))
+    rng.shuffle(numbers)
+    strand = [rng.choice((1, -1)) for _ in range(n + 1)]
+    depths, links = [5.0] * n, []
+    for b in range(bubbles):
+        mine = numbers[b * (arms + 3):(b + 1) * (arms + 3)]
+        start, end = mine[0] * strand[mine[0]], mine[1] * strand[mine[1]]
+        for arm in mine[2:]:
+            links += [(start, arm * strand[arm]), (arm * strand[arm], end)]
+        for arm in mine[3:]:
+            depths[arm - 1] = 0.5
+    case = make_case(n, links, depths=depths, min_depth=1.0)
+    case["expect"] = dict(rounds=arms, low_depth=bubbles * arms, kept_dead_end=0, candidates=bubbles * arms)
+    return case
+
+
+def with_expect(case, **expect):
+    case["expect"] = expect
+    return case
+
+
+def tile_rows(batch):
+    """the rows of part 2 of the boundary table; each states in `expect` the counts that make it the row it is"""
+    rows = {}
+    for t in TILE_SIZES:
+        # n and n_out = n + 2 * 40 at the tile; with n_out the duplications alone carry the unitig count to and over it
+        rows[f"tile: n = {t}"] = with_expect(tile_case(t, t), n=t, n_out=t + 80)
+        rows[f"tile: n_out = {t}"] = with_expect(tile_case(100 + t, t - 80), n=t - 80, n_out=t)
+        # the link entries (the first sort and the two flag scans), the edited entries (the second sort, the out-link scan, the offset search)
+        rows[f"tile: nl = {t}"] = with_expect(tile_case(200 + t, int(t / 2.6) + 1, nl=t), nl=t)
+        rows[f"tile: ne = {t}"] = with_expect(tile_case(300 + t, int((t + 260) / 2.6) + 1, ne=t), ne=t)
+        # the candidates (their scan, the work lists): three times as many unitigs
+        rows[f"tile: candidates = {t}"] = with_expect(tile_case(400 + t, 3 * t, candidates=t), candidates=t, n=3 * t)
+    rows["tile: one duplication carries n_out from 2047 over 2048"] = with_expect(tile_case(7, 2047, n_dup=1), n=2047, n_out=2049)
+    for n in (32767, 32768):      # the link key is 2 * bit_width(2 n) bits wide: 32, then 34 — the first width whose upper half is not zero
+        rows[f"wide keys: n = {n}"] = with_expect(tile_case(500 + (n & 1), n, n_remove=0, n_dup=10, low=0.01), n=n, link_key_bits=2 * bit_width(2 * n))
+    assert rows["wide keys: n = 32767"]["expect"]["link_key_bits"] == 32 and rows["wide keys: n = 32768"]["expect"]["link_key_bits"] == 34
+    for arms in (12, 2 * batch + 1):
+        rows[f"multi-arm bubbles: 300 of {arms} low arms"] = multi_arm_case(300, arms)
+    rows["dense: 4096 unitigs, 2.5 links each, half low"] = with_expect(tile_case(11, 4096, n_remove=0, n_dup=0, link_factor=2.5, low=0.5), n=4096, dense=True)
+    return rows
+
+
+def round_schedule(case, exp, counts):
+    """-> per candidate the round that decides it, by the rule of DESIGN 9l read off the model's edited entries: a candidate is decided in the
+    round after the last larger candidate whose closed neighbourhood meets its own (they share a slot), in the first round without one"""
+    first = {}
+    for a, b in counts["edited"]:
+        first.setdefault(abs(a), {abs(a)}).add(abs(b))
+    slot, rounds = {}, {}
+    for u in range(exp["n_out"], 0, -1):
+        if exp["reason"][u - 1] in (CU.LOW_DEPTH, CU.KEPT_DEAD_END):
+            hood = first.get(u, {u})
+            rounds[u] = 1 + max(slot.get(s, 0) for s in hood)
+            for s in hood:
+                slot[s] = rounds[u]
+    return rounds
+
+
+def row_facts(case, exp, counts, batch):
+    rounds = round_schedule(case, exp, counts)
+    return dict(n=case["n"], n_out=exp["n_out"], nl=len(case["links"]), ne=counts["n_edit"], candidates=counts["n_candidates"], link_key_bits=2 * bit_width(2 * case["n"]),
+                low_depth=exp["reason"].count(CU.LOW_DEPTH), kept_dead_end=exp["reason"].count(CU.KEPT_DEAD_END), rounds=max(rounds.values(), default=0),
+                left_after_a_batch=sum(1 for r in rounds.values() if r > batch))
+
+
+def check_row(name, case, facts, rounds, batch):
+    """what makes the row the row it is, as assertions; rounds: the library's"""
+    expect = case.get("expect", {})
+    for key, want in expect.items():
+        if key != "dense":
+            assert facts[key] == want, (name, key, facts[key], want)
+    assert rounds == facts["rounds"], (name, "rounds", rounds, facts["rounds"])
+    if "expect" in case:
+        assert facts["low_depth"] >= 1, (name, "no deletion: the row passes vacuously")
+    if name.startswith(("tile:", "wide keys", "dense")):
+        assert facts["kept_dead_end"] >= 1, (name, "no dead end")
+    if expect.get("dense"):
+        assert rounds > 2 * batch and facts["low_depth"] > 256 and facts["kept_dead_end"] > 256 and facts["left_after_a_batch"] > 256, (name, facts)
+
+
+_ROWS = {}      # per batch size: the cases, and per row the model's result — built once, shared by the emulation, the device and the guard drivers, read only
+
+
+def boundary_expected(batch, name):
+    """-> (model, facts) of one row: the literal model for the rows at the scale of one wavefront, clean_model_fast for the tile rows (held equal
+    to the literal one up to LITERAL_MAX unitigs by test_fast_model_equals_the_literal_model_on_the_boundary_table)"""
+    cases, cache = boundary_cases(batch), _ROWS[batch][1]
+    if name not in cache:
+        case, counts = cases[name], {}
+        fast = run_model_fast(case, counts)
+        cache[name] = (fast if "expect" in case else run_model(case), row_facts(case, fast, counts, batch))
+    return cache[name]
+
+
 def boundary_cases(batch):
+    if batch not in _ROWS:
+        _ROWS[batch] = (dict(small_rows(batch), **tile_rows(batch)), {})
+    return _ROWS[batch][0]
+
+
+def small_rows(batch):
     cases = {}
     for c in (63, 64, 65):
         cases[f"{c} candidates"] = candidates_case(c)
@@ -264,10 +458,17 @@ def rounds_per_batch(lib_path, device=0):
     return cl.summary["rounds_per_batch"]
 
 
-def check_boundary_table(lib_path, device=0):
+def check_boundary_table(lib_path, device=0, only=None):
+    """only: the rows whose names begin so (a tuple), or "one wavefront" for the rows that state no counts; every row without it"""
     batch = rounds_per_batch(lib_path, device)
-    for name, case in boundary_cases(batch).items():
-        exp, sm = check_case(case, lib_path, device, name)
+    chosen = {name: case for name, case in boundary_cases(batch).items() if only is None or ("expect" not in case if only == "one wavefront" else name.startswith(only))}
+    assert chosen, only
+    for name, case in chosen.items():
+        model, facts = boundary_expected(batch, name)
+        exp, sm = check_case(case, lib_path, device, name, texts=case["n"] <= TEXTS_MAX, exp=model)
+        check_row(name, case, facts, sm["rounds"], batch)
+        if name.startswith("multi-arm"):
+            assert sm["rounds"] == case["expect"]["rounds"] and sm["low_depth"] == case["n"] // (sm["rounds"] + 3) * sm["rounds"] and sm["kept_dead_end"] == 0, name
         if name.startswith("chain of"):
             assert sm["rounds"] == case["n"], (name, sm["rounds"])
         if name.endswith("candidates"):
@@ -281,6 +482,102 @@ def check_boundary_table(lib_path, device=0):
 
 def test_boundary_table(emu):
     assert check_boundary_table(emu)
+
+
+def check_large(case, lib_path, device=0, what=""):
+    """a case beyond the literal model: two runs held to clean_model_fast without the texts, and to each other as bytes -> (model, summary)"""
+    exp = run_model_fast(case)
+    a, b = run_library(case, lib_path, device), run_library(case, lib_path, device)
+    CU.assert_same(a, exp, what)
+    assert CU.cleaned_bytes(a) == CU.cleaned_bytes(b), (what, "two runs")
+    assert (a.summary["launches"], a.summary["read_backs"], a.summary["rounds"]) == (b.summary["launches"], b.summary["read_backs"], b.summary["rounds"]), what
+    sm = a.summary
+    a.close(); b.close()
+    return exp, sm
+
+
+def test_bubbles_beyond_a_tile(emu):
+    """2049 bubbles side by side: one round, 2049 decisions in 33 wavefronts"""
+    _, sm = check_large(candidates_case(2049), emu, what="2049 bubbles")
+    assert sm["rounds"] == 1 and sm["low_depth"] == 2049 and sm["kept_dead_end"] == 0
+
+
+def test_hub_of_degree_4097(emu):
+    """4097 rounds, 513 batches, a range off[2u] .. off[2u + 2] of 4097 entries: the emulation only (16 s here; the guard drivers and the device's
+    launch count are spared)"""
+    hub = hub_case(4097)
+    _, sm = check_case(hub, emu, what="hub of degree 4097", texts=False, exp=run_model_fast(hub))
+    assert sm["rounds"] == 4097 and sm["low_depth"] == 4096 and sm["kept_dead_end"] == 1
+
+
+# ---- the fast model is the literal one ---------------------------------------------------------------------------------------------------------------
+def assert_fast_is_literal(case, what, literal=None):
+    try:
+        literal = run_model(case) if literal is None else literal
+    except CU.CleanError as e:
+        with pytest.raises(CU.CleanError) as fast:
+            run_model_fast(case)
+        assert str(fast.value) == str(e), what
+        return None
+    CU.assert_models_equal(run_model_fast(case), literal, what)
+    return literal
+
+
+def test_fast_model_equals_the_literal_model_on_the_existing_cases():
+    """the known answers' graphs with their options, the named cases, the error list's cases, every case of the four sweeps and of the order and two-run checks"""
+    kats = CU.load_kats()
+    assert_fast_is_literal(fixture_case(kats["low_depth"]["fixture"], min_depth=kats["low_depth"]["min_depth"]), "kat low depth")
+    for kat in kats["duplicate"]:
+        assert_fast_is_literal(fixture_case(kat["fixture"], duplicate=[kat["number"]]), kat["fixture"])
+    gone = []
+    for step in kats["remove"]["steps"]:
+        gone += step["remove"]
+        assert_fast_is_literal(fixture_case(kats["remove"]["fixture"], remove=list(gone)), "kat remove")
+    for name, case in named_cases().items():
+        assert_fast_is_literal(case, name)
+    base = dict(n=5, links=CU.l_line_order(M.closed_set([(1, 2), (2, 3), (3, 4), (3, 5)])), lens=[3] * 5, depths=[4.0] * 5, types=None, alive=[1, 1, 1, 1, 0], seqs=None,
+                remove=[], duplicate=[], min_depth=None)
+    for kw in (dict(remove=[9]), dict(remove=[0]), dict(remove=[5]), dict(duplicate=[6]), dict(remove=[1], duplicate=[2, 7]), dict(duplicate=[1]), dict(duplicate=[3], alive=None),
+               dict(remove=[2], duplicate=[2]), dict(duplicate=[2, 2]), dict(remove=[4], duplicate=[3])):
+        assert assert_fast_is_literal(dict(base, **kw), f"error {kw}") is None
+    for seeds, kw in SWEEPS:
+        for seed in seeds:
+            rng = random.Random(9000 + seed)
+            for i in range(25):
+                assert_fast_is_literal(random_case(rng, **kw), f"seed {seed} case {i}")
+    for seed, count in ((4711, 12), (77, 6)):
+        rng = random.Random(seed)
+        for i in range(count):
+            assert_fast_is_literal(random_case(rng), f"rng {seed} case {i}")
+    for case in (bubbles_with_extras(2, 1, 0), bubbles_with_extras(6, 3, 2), multi_arm_case(50, 12, spare=1400), chain_case(24), chain_case(8, low=2)):
+        assert_fast_is_literal(case, "launch counts")
+
+
+def literal_rows(batch):
+    return [name for name, case in boundary_cases(batch).items() if case["n"] <= LITERAL_MAX]
+
+
+ROW_GROUPS = ("chain", "hub", "tile: n =", "tile: n_out", "tile: nl", "tile: ne", "tile: one", "dense", "other")
+
+
+@pytest.mark.parametrize("group", ROW_GROUPS)
+def test_fast_model_equals_the_literal_model_on_the_boundary_table(emu, group):
+    """every row at or below LITERAL_MAX unitigs (the rows above it are the candidate tiles, the wide keys and the multi-arm bubbles, whose
+    shape at 50 bubbles is among the existing cases' test); in groups, since the literal model takes seconds per tile row"""
+    batch = rounds_per_batch(emu)
+    names = [n for n in literal_rows(batch) if n.startswith(group) or (group == "other" and not n.startswith(ROW_GROUPS[:-1]))]
+    assert names, group
+    for name in names:
+        case = boundary_cases(batch)[name]
+        model, _ = boundary_expected(batch, name)
+        assert_fast_is_literal(case, name, literal=None if "expect" in case else model)
+
+
+def test_every_row_is_in_a_group_or_above_the_literal_model(emu):
+    batch = rounds_per_batch(emu)
+    above = [n for n, c in boundary_cases(batch).items() if c["n"] > LITERAL_MAX]
+    assert all(n.startswith(("tile: candidates", "wide keys", "multi-arm")) for n in above), above
+    assert len(literal_rows(batch)) + len(above) == len(boundary_cases(batch)) and len(above) == 6 + 2 + 2
 
 
 # ---- the random sweep --------------------------------------------------------------------------------------------------------------------------------
@@ -328,8 +625,11 @@ def check_sweep(lib_path, seeds, per_seed=25, device=0, **kw):
     return met
 
 
-@pytest.mark.parametrize("seeds,kw", [((0, 1, 2, 3, 4, 5), {}), ((6, 7, 8, 9, 10, 11), dict(max_unitigs=16, link_factor=1.2)),
-                                      ((12, 13, 14, 15, 16, 17), dict(max_unitigs=40, link_factor=0.9)), ((18, 19, 20, 21, 22, 23), dict(max_unitigs=8, link_factor=2.0))])
+SWEEPS = [((0, 1, 2, 3, 4, 5), {}), ((6, 7, 8, 9, 10, 11), dict(max_unitigs=16, link_factor=1.2)),
+          ((12, 13, 14, 15, 16, 17), dict(max_unitigs=40, link_factor=0.9)), ((18, 19, 20, 21, 22, 23), dict(max_unitigs=8, link_factor=2.0))]
+
+
+@pytest.mark.parametrize("seeds,kw", SWEEPS)
 def test_sweep(emu, seeds, kw):
     met = check_sweep(emu, seeds, **kw)
     assert met["removed"] and met["duplicated"] and met["low"] and met["dead_end"] and met["rounds_above_one"], met
@@ -338,7 +638,7 @@ def test_sweep(emu, seeds, kw):
 def test_sweep_is_order_free(emu, monkeypatch):
     """the emulation visits the logical threads descending and shuffled: the products are the same bytes"""
     rng = random.Random(4711)
-    cases = [random_case(rng) for _ in range(12)]
+    cases = [random_case(rng) for _ in range(12)] + beyond_a_wavefront(rounds_per_batch(emu))
     want = []
     for case in cases:
         cl = run_library(case, emu)
@@ -457,9 +757,16 @@ def test_errors(emu):
 
 
 # ---- two runs, and what the launches follow -----------------------------------------------------------------------------------------------------------
-def check_two_runs_identical(lib_path, device=0):
+def beyond_a_wavefront(batch):
+    """two rows in which the work list is compacted by many wavefronts, whose atomics the device orders anew in every run: a random graph of
+    2049 unitigs and the multi-arm bubbles across a batch edge"""
+    rows = boundary_cases(batch)
+    return [rows["tile: n = 2049"], rows[f"multi-arm bubbles: 300 of {2 * batch + 1} low arms"]]
+
+
+def check_two_runs_identical(lib_path, device=0, more=()):
     rng = random.Random(77)
-    for case in [random_case(rng) for _ in range(6)] + [hub_case(65), chain_case(11)]:
+    for case in [random_case(rng) for _ in range(6)] + [hub_case(65), chain_case(11)] + beyond_a_wavefront(rounds_per_batch(lib_path, device)) + list(more):
         a, b = run_library(case, lib_path, device), run_library(case, lib_path, device)
         assert CU.cleaned_bytes(a) == CU.cleaned_bytes(b)
         assert (a.summary["launches"], a.summary["read_backs"]) == (b.summary["launches"], b.summary["read_backs"])
@@ -496,6 +803,13 @@ def check_launch_counts(lib_path, device=0):
     assert [r["rounds"] for r in runs] == [batch, 2 * batch, 3 * batch]
     assert runs[1]["launches"] - runs[0]["launches"] == runs[2]["launches"] - runs[1]["launches"] > 0, runs
     assert runs[1]["read_backs"] - runs[0]["read_backs"] == runs[2]["read_backs"] - runs[1]["read_backs"] == 1, runs
+    # bubbles of 12 arms, 50 and 300 of them: 12 rounds each, one workgroup and several — the same launches and read-backs
+    few_bubbles, many_bubbles = multi_arm_case(50, 12, spare=1400), multi_arm_case(300, 12)
+    a, b = check_case(few_bubbles, lib_path, device, "50 bubbles of 12 arms")[1], check_case(many_bubbles, lib_path, device, "300 bubbles", exp=run_model_fast(many_bubbles))[1]
+    assert a["rounds"] == b["rounds"] == 12 and a["low_depth"] == 600 and b["low_depth"] == 3600
+    for bits in (lambda n: 2 * bit_width(2 * n), lambda n: bit_width(2 * n - 1)):      # (the sorts' passes follow the key widths: the spare unitigs keep both inside one digit)
+        assert (bits(few_bubbles["n"]) + 7) // 8 == (bits(many_bubbles["n"]) + 7) // 8
+    assert (a["launches"], a["read_backs"]) == (b["launches"], b["read_backs"]), (a, b)
     # within one batch the read-backs do not move at all
     few, more = check_case(chain_case(batch, low=2), lib_path, device, "2 rounds")[1], check_case(chain_case(batch), lib_path, device, "a batch of rounds")[1]
     assert few["rounds"] < more["rounds"] and few["read_backs"] == more["read_backs"] and few["launches"] == more["launches"], (few, more)
